@@ -8,6 +8,10 @@ update) over one batch of B motions per GPU (BASELINE.json configs[2]: B=16, T=3
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
     python bench.py --gpus 8            (no launcher: starts the N ranks itself as fresh child processes, before any GPU call)
+
+A plain run sets up, warms up, times --steps steps, writes their outputs when --dump-outputs is given and prints the line.  Everything else
+the line can carry (full_loop, facade, roofline, cpu_baseline and the fp32_split / bf16_fp8 / eval_items side objects) is measured with
+--full only and is null otherwise; the --no-* options below drop single parts of a --full run.
 """
 import argparse
 import json
@@ -103,7 +107,14 @@ def main():
                          "one weight set (mmdm_create_shared), and as ragged batches (mmdm_begin_ragged); reports items/s, roofline and cpu_baseline per strategy")
     ap.add_argument("--eval-max-rows", type=int, default=4800, help="--eval-items: frames per ragged batch (default 4800 = 16 x 300)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous check without a GPU: ranks meet on gloo, time a barrier, rank 0 prints a line")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: full_loop, facade, roofline, cpu_baseline and the "
+                                                        "fp32_split / bf16_fp8 / eval_items side objects (a plain run leaves them null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step left (x, x2, pred_xstart, pred_xstart2, model_out: rank 0's shard) "
+                         "as DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded sample of the elements beyond that)")
     args = ap.parse_args()
+    if args.dump_outputs and args.eval_items:
+        ap.error("--dump-outputs writes the state of the headline step; --eval-items times another caller")
     if args.cpu_worker:
         return cpu_worker(*args.cpu_worker)
 
@@ -188,8 +199,6 @@ def main():
     cond, xT = synthetic_inputs(B, T, seed_cond=1 + 1000 * rank, seed_x=2 + 1000 * rank, single=single)   # each rank = its own shard of the batch
     cond, xT = cond.to(device), xT.to(device)
     use_graph = not args.no_graph
-    if args.warmup + args.steps > S:
-        raise SystemExit("warmup + steps must be <= %d (the steps of %s)" % (S, args.sampler))
 
     def barrier():
         if dist.is_initialized():
@@ -197,10 +206,10 @@ def main():
         torch.cuda.synchronize()
 
     smp.begin(cond, xT)                      # inputs resident in HBM before the timed region
-    smp.run(args.warmup, use_graph)          # untimed warm-up (includes the graph capture)
+    done = run_steps(smp, args.warmup, use_graph)        # untimed warm-up (includes the graph capture)
     barrier()
     t0 = time.perf_counter()
-    smp.run(args.steps, use_graph)
+    run_steps(smp, args.steps, use_graph, done)
     barrier()
     dt = time.perf_counter() - t0
     tmax = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -214,6 +223,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     rank_ms = {"min": round(min(per_rank) / args.steps * 1e3, 3), "max": round(max(per_rank) / args.steps * 1e3, 3)}
     finite = bool(torch.isfinite(smp.state()["x"]).all().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, smp.state())
 
     # dominant kernel of a precision mode: live HIP-event timing of every GEMM launch of an eager pass, on the handle's stream
     def live_roofline(smp, prec, with_clock=True):
@@ -277,7 +288,7 @@ def main():
             roof["clock"] = {"error": repr(e)}
         return roof
 
-    roof = live_roofline(smp, args.precision) if (rank == 0 and args.profile_steps > 0) else None
+    roof = live_roofline(smp, args.precision) if (args.full and rank == 0 and args.profile_steps > 0) else None
 
     if dist.is_initialized():
         dist.barrier()
@@ -285,17 +296,17 @@ def main():
     # Same workload, same inputs, in the fp32-split mode (fp32-accurate GEMMs on the bf16 matrix cores: DESIGN.md 6c).  Reported beside the
     # headline, never as it: the headline stays the native-fp32 parity path that the reference-captured goldens pin end to end.
     alt = None
-    if world == 1 and args.precision == "fp32" and not args.no_alt and not single:
+    if args.full and world == 1 and args.precision == "fp32" and not args.no_alt and not single:
         alt_smp = Sampler(d_heads=8, m_heads=8, max_batch=B, max_frames=T, single_only=single, precision="fp32_split", **FULL_DIMS)
         alt_smp.load_state_dict(sd_cpu)
         alt_smp.set_norm_stats(stats["mean_hml"], stats["std_hml"], stats["mean_ih"], stats["std_ih"])
         alt_smp.prepare()
         alt_smp.set_schedule(args.sampler)
         alt_smp.begin(cond, xT)
-        alt_smp.run(args.warmup, use_graph)
+        alt_done = run_steps(alt_smp, args.warmup, use_graph)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        alt_smp.run(args.steps, use_graph)
+        run_steps(alt_smp, args.steps, use_graph, alt_done)
         torch.cuda.synchronize()
         a_ms = (time.perf_counter() - t1) / args.steps * 1e3
         # how far the two modes are apart after the same number of steps from the same state (fp32 rounding noise level)
@@ -337,18 +348,18 @@ def main():
     # a throughput configuration with a stated accuracy, reported beside the headline, never as it.  Its `roofline` prices
     # the fp8 launches against the 5 PFLOP/s dense fp8 peak and the bf16 launches against 2.5 (live HIP-event pairs, as above).
     fp8 = None
-    if world == 1 and args.precision == "fp32" and not args.no_side and not single and not args.facade:
+    if args.full and world == 1 and args.precision == "fp32" and not args.no_side and not single and not args.facade:
         f_smp = Sampler(d_heads=8, m_heads=8, max_batch=B, max_frames=T, precision="bf16_fp8", **FULL_DIMS)
         f_smp.load_state_dict(sd_cpu)
         f_smp.set_norm_stats(stats["mean_hml"], stats["std_hml"], stats["mean_ih"], stats["std_ih"])
         f_smp.prepare()
         f_smp.set_schedule(args.sampler)
         f_smp.begin(cond, xT)
-        f_smp.run(max(args.warmup, 5), use_graph)
+        f_done = run_steps(f_smp, max(args.warmup, 5), use_graph)
         torch.cuda.synchronize()
         nst = max(args.steps, 20)
         t1 = time.perf_counter()
-        f_smp.run(nst, use_graph)
+        run_steps(f_smp, nst, use_graph, f_done)
         torch.cuda.synchronize()
         f_ms = (time.perf_counter() - t1) / nst * 1e3
         fp8 = {"mode": "bf16_fp8 (BASELINE configs[4]: bf16 path, QKV / cross-attention input / FFN GEMMs on fp8 e4m3 operands through v_mfma_scale_f32_32x32x64_f8f6f4; "
@@ -364,7 +375,7 @@ def main():
     # The reference's evaluation caller (src/evaluation/datasets.py:100-116: one forward_test per item, the item's own length) on a few items:
     # the sequential loop as shipped against ragged batches, bit-identity asserted in the object (bench.py --eval-items N is the full line)
     ev = None
-    if world == 1 and args.precision == "fp32" and not args.no_side and not single and not args.facade and args.sampler == "ddim1000":
+    if args.full and world == 1 and args.precision == "fp32" and not args.no_side and not single and not args.facade and args.sampler == "ddim1000":
         try:
             e = eval_items_bench(args, device, rank, world, as_side=True)
             ev = {k: e[k] for k in ("metric", "value", "unit", "strategies", "bit_identical_to_sequential", "roofline", "graph_cache")}
@@ -375,7 +386,7 @@ def main():
     # The metric itself, not an extrapolation: one whole sample() from x_T to x_0 (S graph replays + the begin() set-up), every rank
     # on its own shard, wall time = max over ranks.
     full = None
-    if not args.no_full_loop:
+    if args.full and not args.no_full_loop:
         barrier()
         t1 = time.perf_counter()
         out = smp.sample(cond, xT, use_graph=use_graph)
@@ -392,7 +403,7 @@ def main():
     # is kept) and forward_test (src/evaluation/datasets.py:101-116), text conditioning precomputed (`cond` in the batch: the CLIP tower is
     # upstream of this path).  Second calls: the (B, T, S) graph and the workspace exist.
     fac = None
-    if model is not None and rank == 0:
+    if args.full and model is not None and rank == 0:
         batch = {"cond": cond, "x_T": xT, "motion_lens": torch.full((B, 1), T, dtype=torch.long)}
         fac = {}
         for name, fn in (("forward_test", model.forward_test), ("forward", model.forward)):
@@ -407,7 +418,7 @@ def main():
             del o
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:       # reported at N=1 only (the other ranks of an N>1 run would idle behind it)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:       # reported at N=1 only (the other ranks of an N>1 run would idle behind it)
         cpu = cpu_baseline(sd_cpu, stats, T, args.cpu_steps, single, args.sampler, S, B, whole_host=not args.no_whole_host)
 
     if rank == 0:
@@ -441,6 +452,35 @@ def main():
         smp.close()
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+def run_steps(smp, n, use_graph, done=0):
+    """n DDIM steps of the begun call, `done` of its S steps already run.  Past the schedule's last step the chains go on from its first
+    one as they stand (Sampler.seek), so that --warmup and --steps may exceed S.  Returns the steps of the schedule run so far."""
+    S = smp.schedule.num_timesteps
+    while n > 0:
+        if done == S:
+            smp.seek(S - 1)
+            done = 0
+        k = min(n, S - done)
+        smp.run(k, use_graph)
+        n, done = n - k, done + k
+    return done
+
+
+def dump_outputs(path, state, budget=60 << 20):
+    """The arrays of a Sampler.state() as <path>/<name>.npy, float32.  An array larger than its equal share of `budget` bytes (60 MiB: the files
+    stay below 64 MB with their headers) is written as a fixed sample of its elements (flattened, seeded index set in ascending order), so
+    that two builds given the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in state.items() if v is not None}
+    share = budget // len(arrays) // 4
+    for name, v in arrays.items():
+        a = v.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def loop_clock(precision, M, peak, achieved):

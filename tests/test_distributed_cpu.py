@@ -207,3 +207,46 @@ def test_bench_stamps_the_library_and_names_the_same_batch_reference_point(monke
     assert ref and ref["measured_in_this_run"] is False and ref["n_gpus"] == 1 and ref["per_gpu_batch"] == 32 and ref["source"].startswith("profiles/r")
     assert abs(ref["value"] - 32 / (ref["ms_per_step"] * 1e-3 * 1000)) < 1e-3
     assert bench.n1_same_batch(16, "fp32") is None and bench.n1_same_batch(32, "bf16") is None
+
+
+def test_bench_steps_run_past_the_schedule_and_outputs_fit_the_budget(tmp_path):
+    """--warmup + --steps may exceed the S steps of the schedule: the chains go on from its first step (seek), and every requested step runs.
+    --dump-outputs writes every array of the state as float32 .npy, whole when the 64 MB budget allows and as the same seeded sample otherwise."""
+    import importlib.util
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test3", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class FakeSampler:
+        class schedule:
+            num_timesteps = 50
+
+        def __init__(self):
+            self.calls = []
+
+        def run(self, n, use_graph):
+            assert 0 < n <= 50
+            self.calls.append(("run", n))
+
+        def seek(self, i):
+            self.calls.append(("seek", i))
+
+    s = FakeSampler()
+    done = bench.run_steps(s, 3, True)
+    assert bench.run_steps(s, 120, True, done) == 23
+    assert s.calls == [("run", 3), ("run", 47), ("seek", 49), ("run", 50), ("seek", 49), ("run", 23)]
+    assert bench.run_steps(FakeSampler(), 0, True) == 0
+
+    g = torch.Generator().manual_seed(0)
+    state = {"x": torch.randn(2, 3, 4, generator=g), "x2": torch.randn(2, 3, 4, generator=g), "model_out": None}
+    bench.dump_outputs(str(tmp_path / "a"), state)
+    assert sorted(os.listdir(tmp_path / "a")) == ["x.npy", "x2.npy"]
+    x = np.load(tmp_path / "a" / "x.npy")
+    assert x.dtype == np.float32 and np.array_equal(x, state["x"].numpy())
+    bench.dump_outputs(str(tmp_path / "b"), state, budget=2 * 4 * 10)
+    bench.dump_outputs(str(tmp_path / "c"), state, budget=2 * 4 * 10)
+    xs = np.load(tmp_path / "b" / "x.npy")
+    assert xs.shape == (10,) and np.array_equal(xs, np.load(tmp_path / "c" / "x.npy")) and np.isin(xs, x.reshape(-1)).all()
+    assert sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in os.listdir(tmp_path / "b")) <= 2 * 4 * 10

@@ -237,7 +237,7 @@ def test_facade_level_sharded_sampling_on_rccl_world_1(tmp_path, golden):
         dist.destroy_process_group()
 
 
-def test_bench_runs_its_rccl_path_under_torchrun_on_the_gpu_box():
+def test_bench_runs_its_rccl_path_under_torchrun_on_the_gpu_box(tmp_path):
     """`bench.py` as the driver launches it for N > 1 -- `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` -- with
     N = 1 and MMDM_BENCH_FORCE_DIST=1, as a CHILD process: the RCCL init -> weight broadcast -> barrier -> all_gather / all_reduce of the
     timings really execute on this box (the CPU suite only covers the launcher with --dry-run on gloo), at the per-GPU batch of BASELINE
@@ -253,7 +253,7 @@ def test_bench_runs_its_rccl_path_under_torchrun_on_the_gpu_box():
     env.update(MMDM_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "32", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt", "--no-side", "--no-full-loop",
-           "--profile-steps", "0"]
+           "--profile-steps", "0", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -267,3 +267,10 @@ def test_bench_runs_its_rccl_path_under_torchrun_on_the_gpu_box():
     assert line["roofline"] is None or line["roofline"]["traffic"] is None
     # every line says which library it ran: the in-tree build, no MMDM_LIB override
     assert line["mmdm_version"].startswith("gfx950;") and line["lib"] == os.path.join("mixermdm_amd", "libmmdm_hip.so") and line["lib_override"] is False
+    # --dump-outputs: the state the last timed step left, float32, within 64 MB (the 32-motion state is larger: a seeded sample of it)
+    names = sorted(os.listdir(tmp_path / "out"))
+    assert names == ["model_out.npy", "pred_xstart.npy", "pred_xstart2.npy", "x.npy", "x2.npy"]
+    for n in names:
+        a = np.load(tmp_path / "out" / n)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all()
+    assert sum(os.path.getsize(tmp_path / "out" / n) for n in names) <= 64 * 10 ** 6

@@ -4,7 +4,7 @@
 # change?' is answered.   usage: tools/ab_lib.sh variants/libmmdm_other.so [precision ...]     (default: fp32, two-stream and one-stream)
 OTHER=${1:-variants/libmmdm_old.so}; shift
 MODES=${@:-fp32}
-Q="--no-cpu-baseline --no-alt --no-side --no-full-loop --no-clock --steps 20 --warmup 5"
+Q="--full --no-cpu-baseline --no-alt --no-side --no-full-loop --no-clock --steps 20 --warmup 5"
 for m in $MODES; do
   for i in 1 2; do
     for lib in other tree; do

@@ -10,8 +10,8 @@ for pm in fp32: fp32_split:_fp32_split bf16_fp8:_bf16_fp8; do
 done
 f=gpurun_out/prof_b1_$TAG/summary_fp32/gemm_traffic.json; [ -f $f ] && cp $f profiles/gemm_traffic_b1t299.json       # tools/profile_b1.sh of the same call
 f=gpurun_out/prof_ragged_$TAG/summary_pmc/gemm_traffic.json; [ -f $f ] && cp $f profiles/gemm_traffic_ragged.json        # tools/profile_ragged.sh of the same call
-Q="--no-cpu-baseline --no-alt --no-side --no-full-loop"
-python bench.py > $O/default.json 2> $O/default.err                                    # the driver's command: headline + fp32_split + full loop + CPU port
+Q="--full --no-cpu-baseline --no-alt --no-side --no-full-loop"
+python bench.py --full > $O/default.json 2> $O/default.err                             # the default line with --full: headline + fp32_split + full loop + CPU port
 python bench.py --workload single $Q > $O/single.json 2> $O/single.err                  # configs[1]
 python bench.py --precision bf16 $Q > $O/bf16.json 2> $O/bf16.err
 python bench.py --precision bf16_fp8 $Q > $O/bf16_fp8.json 2> $O/bf16_fp8.err           # configs[4] arithmetic at B = 16
@@ -20,9 +20,9 @@ python bench.py --batch 32 $Q > $O/b32.json 2> $O/b32.err                       
 python bench.py --batch 32 --precision fp32_split $Q > $O/b32_split.json 2> $O/b32_split.err
 # the reference's own call shapes (src/scripts/infer/mixermdm.py:73,117-124; src/evaluation/datasets.py:58,100-116): B = 1 and B = 15, T = 299, ddim50, through the
 # facade (one whole MixerMDM.forward / forward_test each), the CPU port timing the SAME loop in full; and configs[0] (single-person, B = 1, T = 120, ddim50)
-python bench.py --batch 1 --frames 299 --sampler ddim50 --facade --steps 20 --warmup 3 > $O/infer_b1.json 2> $O/infer_b1.err
-python bench.py --batch 15 --frames 299 --sampler ddim50 --facade --steps 20 --warmup 3 --no-cpu-baseline > $O/infer_b15.json 2> $O/infer_b15.err
-python bench.py --workload single --batch 1 --frames 120 --sampler ddim50 --steps 20 --warmup 3 > $O/configs0.json 2> $O/configs0.err
+python bench.py --full --batch 1 --frames 299 --sampler ddim50 --facade --steps 20 --warmup 3 > $O/infer_b1.json 2> $O/infer_b1.err
+python bench.py --full --batch 15 --frames 299 --sampler ddim50 --facade --steps 20 --warmup 3 --no-cpu-baseline > $O/infer_b15.json 2> $O/infer_b15.err
+python bench.py --full --workload single --batch 1 --frames 120 --sampler ddim50 --steps 20 --warmup 3 > $O/configs0.json 2> $O/configs0.err
 # the reference's evaluation caller (src/evaluation/datasets.py:100-116): 64 items of their own lengths as the sequential loop, in-flight handles and ragged batches
 python bench.py --eval-items 64 > $O/eval64.json 2> $O/eval64.err
 python bench.py --eval-items 64 --precision fp32_split --no-cpu-baseline > $O/eval64_split.json 2> $O/eval64_split.err

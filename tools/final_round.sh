@@ -11,7 +11,7 @@ bash tools/profile_fp8_b64.sh $TAG > gpurun_out/profile_fp8_b64_$TAG.log 2>&1
 FP8_ONLY=packed-t FP8_SHAPES=qkv,ffn2 bash tools/pmc_fp8.sh $TAG > gpurun_out/pmc_fp8_$TAG.log 2>&1
 FP8_ONLY=persist FP8_SHAPES=qkv bash tools/pmc_fp8.sh ${TAG}_persist > gpurun_out/pmc_fp8_${TAG}_persist.log 2>&1
 O=gpurun_out/probes_$TAG; mkdir -p $O
-[ -x variants/pk8 ] && ./variants/pk8 > $O/mfma_sustained.txt 2>&1
+mkdir -p build && hipcc --offload-arch=gfx950 -O3 tools/mfma_peak_fp8.hip -o build/mfma_peak_fp8 && ./build/mfma_peak_fp8 > $O/mfma_sustained.txt 2>&1
 python tools/gemm_fp8_bench.py 2>&1 | grep -v amdgpu.ids > $O/gemm_fp8_bench.txt
 FP8_M=76800 FP8_SHAPES=qkv,caq,cakv,ffn1 python tools/gemm_fp8_bench.py 2>&1 | grep -v amdgpu.ids > $O/gemm_fp8_bench_b64.txt
 python tools/fp8_step_ab.py 2>&1 | grep -v amdgpu.ids > $O/fp8_step_ab.txt

@@ -6,7 +6,7 @@ TAG=${1:-r06}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_b1_$TAG
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --batch 1 --frames 299 --sampler ddim50 --facade --no-cpu-baseline --no-alt --no-side --no-full-loop --no-clock"
+B="$R/bench.py --full --batch 1 --frames 299 --sampler ddim50 --facade --no-cpu-baseline --no-alt --no-side --no-full-loop --no-clock"
 MMDM_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python3 $B --steps 20 --warmup 3 > $O/serial.json 2> $O/serial.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/overlap -- python3 $B --steps 20 --warmup 3 > $O/overlap.json 2> $O/overlap.err
 # (PMC passes: the same sampler without the facade's two whole 50-step calls -- counter collection serialises every launch at milliseconds each)

@@ -6,7 +6,7 @@ TAG=${1:-r06}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_fp8_b64_$TAG
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --precision bf16_fp8 --batch 64 --no-cpu-baseline --no-alt --no-side --no-full-loop --no-clock"
+B="$R/bench.py --full --precision bf16_fp8 --batch 64 --no-cpu-baseline --no-alt --no-side --no-full-loop --no-clock"
 MMDM_NO_OVERLAP=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python3 $B --steps 6 --warmup 2 > $O/serial.json 2> $O/serial.err
 P="$B --steps 2 --warmup 1 --no-graph --profile-steps 0"
 for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
