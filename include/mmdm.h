@@ -28,7 +28,6 @@
  *                        precision overlap bit-exactly (tests/test_gpu_ragged.py); the switch exists so that overlap can be ruled out in the field.
  *   MMDM_NO_PACK=1       keep the low-precision weight twins of precision 1-3 in row-major planes instead of MFMA fragment order (the
  *                        packed and the plane kernels are bit-identical; tests/test_gpu_packed_modes.py compares them).
- *   MMDM_QKP / MMDM_NO_QKP / MMDM_NO_BF16_PV   precision >= 1: force / forbid the bf16-plane Q K^T and the bf16 P V forms of the attention.
  * All of them are read ONCE, by mmdm_create, into the handle: a handle's behaviour never changes after it exists, and the stateless kernels
  * of section 1 read no environment at all.  The library exports exactly the symbols this header declares (hidden visibility otherwise);
  * section 4 is the one diagnostic entry point the scripts under tools/ use.

@@ -135,8 +135,21 @@ struct LayerWB {         // bf16 twins of the stack GEMM weights (precision >= 1
     float *sa_in_s = nullptr, *ca_in_s = nullptr, *f1_s = nullptr, *f2_s = nullptr;
 };
 
+// Operand form of a stack's attention: what its Q|K|V projections write and what the attention kernel reads.  The enumerators are the
+// projection GEMMs' output modes.
+//   F32    fp32 projection rows -> the fp32 attention kernel (precision 0, and every precision at a head size other than 64 / 128)
+//   BF16   bf16 rows only (Q|K|V, K|V, Q in Scratch::qk / kvp) -> the all-bf16 attention, P.V included (precision 1 and 3)
+//   SPLIT  the two fp16 planes of the fp32-split mode instead of fp32 rows (same bytes) -> the attention on the planes (precision 2)
+enum class Form : int { F32 = 0, BF16 = 1, SPLIT = 2 };
+
+Form stack_form(int precision, int dh) {
+    if (precision == 0 || (dh != 64 && dh != 128)) return Form::F32;
+    return precision == 2 ? Form::SPLIT : Form::BF16;
+}
+
 struct StackW {          // a transformer stack: denoiser blocks or Influence blocks
     int D = 0, F = 0, L = 0, H = 0, n_ada = 0;
+    Form form = Form::F32;
     bool has_ca = false;
     bool w_packed = false;                      // low-precision weight twins stored in MFMA fragment order (gemm_splitw_kernel / gemm_bf16w_kernel take W straight from global memory)
     float *ada_w = nullptr, *ada_b = nullptr;   // [L*n_ada*2D, D], [L*n_ada*2D]  (slots: sa, [ca_q, ca_kv,] ffn)
@@ -166,7 +179,7 @@ struct ModuleW {         // denoiser or mixer front/back ends
 struct Scratch {          // transformer-stack work buffers (one set per concurrently running stack)
     float *h = nullptr, *xn = nullptr, *qkv = nullptr, *kv = nullptr, *att = nullptr, *f1 = nullptr;
     float *xp = nullptr;      // [2][rows][NFP] repacked pose operands of the embedding GEMMs (fp32), or [2][2 planes][rows][NFS] fp16
-    void *qk = nullptr, *kvp = nullptr;   // precision >= 1: bf16 plane copies of the attention's Q|K ([planes][R][2D]) and cross-attention K ([planes][R][D])
+    void *qk = nullptr, *kvp = nullptr;   // Form::BF16 stacks: bf16 projections, Q|K|V or cross-attention Q ([R][3D]) and cross-attention K|V ([R][2D])
     float* xs = nullptr;                  // precision == 3: per-row scales of the fp8 AdaLN output in xn
 };
 
@@ -282,9 +295,9 @@ struct mmdm_handle_s {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork2 = nullptr, ev_join2 = nullptr;
     bool overlap = true;
     // switches read from the environment ONCE, at mmdm_create (include/mmdm.h lists them): a handle's behaviour never changes afterwards
-    bool force_qkp = false, no_qkp = false, no_pvb = false, no_pack = false;      // MMDM_QKP, MMDM_NO_QKP, MMDM_NO_BF16_PV, MMDM_NO_PACK
-    bool no_split_embed = false;                                                  // MMDM_NO_SPLIT_EMBED
-    bool no_split_cond = false;                                                   // MMDM_NO_SPLIT_COND
+    bool no_pack = false;                   // MMDM_NO_PACK
+    bool no_split_embed = false;            // MMDM_NO_SPLIT_EMBED
+    bool no_split_cond = false;             // MMDM_NO_SPLIT_COND
 
     Prof prof;
 };
@@ -330,6 +343,7 @@ void add_ignored(mmdm_handle h, const std::string& name) {
 
 int build_stack(mmdm_handle h, StackW& st, const std::string& pfx, int D, int F, int L, int H, bool has_ca, bool ca_keys_ignored) {
     st.D = D; st.F = F; st.L = L; st.H = H; st.has_ca = has_ca; st.n_ada = has_ca ? 4 : 2;
+    st.form = stack_form(h->cfg.precision, D / H);
     RC(dalloc(h, &st.ada_w, (size_t)L * st.n_ada * 2 * D * D));
     RC(dalloc(h, &st.ada_b, (size_t)L * st.n_ada * 2 * D));
     if (h->cfg.precision >= 1 && D % 64 == 0) {       // two fp16 planes [2][L*n_ada*2D][D]: as many bytes as the fp32 matrix
@@ -543,40 +557,32 @@ struct StackRun {
     int l0 = 0;             // first block to run (the "dual_individual" quirk runs only the last block on person b)
 };
 
-// h [nseq*T, D] is updated in place through the L blocks (TransformerBlockDoubleCond / TransformerBlock / InfluenceBlockCross).
 // bf16-operand GEMM with the same accounting as linear()
-struct Second {           // optional second GEMM output: leading columns also as bf16 plane(s) for the attention kernel
-    void* p = nullptr;
-    int ld = 0, cols = 0;
-    size_t plane = 0;
-};
-
 int linear_b(const Ctx& c, const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int out_bf16, int M, int N, int K,
-             int epi = MMDM_EPI_BIAS, const float* extra = nullptr, int ld_extra = 0, Second s2 = Second()) {
+             int epi = MMDM_EPI_BIAS, const float* extra = nullptr, int ld_extra = 0) {
     RC(prof_begin(c, 0, 2.0 * M * N * K, 2.0 * ((double)M * K + (double)N * K) + (out_bf16 ? 2.0 : 4.0) * M * N * (epi == MMDM_EPI_BIAS_RESID ? 2 : 1)));
-    RC(mmdm_linear_bf16_ex(A, lda, W, ldw, bias, C, ldc, out_bf16, M, N, K, epi, extra, ld_extra, 0, s2.p, s2.ld, s2.cols, c.st));
+    RC(mmdm_linear_bf16_ex(A, lda, W, ldw, bias, C, ldc, out_bf16, M, N, K, epi, extra, ld_extra, 0, nullptr, 0, 0, c.st));
     return prof_end(c, 0);
 }
 
 // fp8-operand GEMM (precision == 3): A fp8 + per-row scales (nullptr = unit), W fp8 + per-output-channel scales (gemm_bf16.hip, ET = 1)
 int linear_8(const Ctx& c, const void* A, int lda, const float* a_scale, const void* W, int ldw, const float* w_scale, const float* bias, void* C, int ldc,
-             int out_mode, int M, int N, int K, int epi, const float* extra, int ld_extra, Second s2 = Second(), float a_const = 1.f, float out_scale = 1.f) {
+             int out_mode, int M, int N, int K, int epi, const float* extra, int ld_extra, float a_const = 1.f, float out_scale = 1.f) {
     RC(prof_begin(c, 2, 2.0 * M * N * K, 1.0 * ((double)M * K + (double)N * K) + (out_mode == 0 ? 4.0 : out_mode == 1 ? 2.0 : 1.0) * M * N * (epi == MMDM_EPI_BIAS_RESID ? 2 : 1)));
-    RC(mmdm_linear_fp8_ex(A, lda, a_scale, W, ldw, w_scale, bias, C, ldc, out_mode, M, N, K, epi, extra, ld_extra, 0, s2.p, s2.ld, s2.cols, a_const, out_scale, c.st));
+    RC(mmdm_linear_fp8_ex(A, lda, a_scale, W, ldw, w_scale, bias, C, ldc, out_mode, M, N, K, epi, extra, ld_extra, 0, nullptr, 0, 0, a_const, out_scale, c.st));
     return prof_end(c, 2);
 }
 
 // fp32-split GEMM (precision == 2): A and W as two fp16 planes, fp32 accuracy on the 16-bit matrix cores (gemm_split.hip)
 int linear_s(const Ctx& c, const void* A, int lda, size_t a_plane, const void* W, int ldw, size_t w_plane, const float* bias, void* C, int ldc,
-             size_t c_plane, int out_split, int M, int N, int K, int epi, const float* extra, int ld_extra, Second s2 = Second(), int period = 0) {
+             size_t c_plane, int out_split, int M, int N, int K, int epi, const float* extra, int ld_extra, int period = 0) {
     const int cls = c.h && c.h->cfg.precision != 2 ? 3 : 0;       // in a bf16 / fp8 handle this is one of the fp32-accurate side GEMMs
     RC(prof_begin(c, cls, 2.0 * M * N * K, 2.0 * MMDM_SPLIT_NPL * ((double)M * K + (double)N * K) + 4.0 * M * N * (epi == MMDM_EPI_BIAS_RESID ? 2 : 1)));
     RC(mmdm_linear_split_ex(A, lda, (int64_t)a_plane, W, ldw, (int64_t)w_plane, bias, C, ldc, (int64_t)c_plane, out_split, M, N, K, epi, extra, ld_extra, period,
-                            s2.p, s2.ld, (int64_t)s2.plane, s2.cols, c.st));
+                            nullptr, 0, 0, 0, c.st));
     return prof_end(c, cls);
 }
 
-// attention whose Q K^T runs on the bf16 matrix cores from the plane copies written by the projection GEMMs
 // algorithmic work of one attention launch: 4 dh (T (T + 1)) per (sequence, head) -- summed over the items' own lengths in a ragged batch
 double attn_flops(const Ctx& c, int nseq, int H, int Tq, int Tk, int dh) {
     if (c.rag()) return 4.0 * (nseq / c.g->B) * H * dh * c.g->tt1;
@@ -593,12 +599,13 @@ const mmdm_rag_seq* rag_seq(const Ctx& c, int nseq, mmdm_rag_seq& tmp) {
     return &tmp;
 }
 
-int attention_p(const Ctx& c, const void* Qp, int ldq, size_t q_plane, const void* Kp, int ldk, size_t k_plane, int np, const float* V, int ldv, void* O, int ldo,
-                int out_mode, int nseq, int Tq, int Tk, int H, int dh, int shift, const void* Vp = nullptr, int ldvp = 0, size_t v_plane = 0) {
+// attention on 16-bit Q, K and V on the matrix cores: `np` = 1 (bf16 rows) or 2 (the two fp16 planes of the fp32-split mode)
+int attention_p(const Ctx& c, const void* Qp, int ldq, size_t q_plane, const void* Kp, int ldk, size_t k_plane, int np, const void* Vp, int ldvp, size_t v_plane,
+                void* O, int ldo, int out_mode, int nseq, int Tq, int Tk, int H, int dh, int shift) {
     mmdm_rag_seq tmp;
     RC(prof_begin(c, 1, attn_flops(c, nseq, H, Tq, Tk, dh), attn_bytes(c, nseq, H, Tq, Tk, dh)));
-    RC(mmdm_attention_planes_ex(Qp, ldq, (int64_t)q_plane, Kp, ldk, (int64_t)k_plane, np, V, ldv, Vp, ldvp, (int64_t)v_plane, O, ldo, out_mode, 0, nseq, Tq, Tk, H, dh, shift, c.st,
-                                rag_seq(c, nseq, tmp)));
+    RC(mmdm_attention_planes_ex(Qp, ldq, (int64_t)q_plane, Kp, ldk, (int64_t)k_plane, np, nullptr, 0, Vp, ldvp, (int64_t)v_plane, O, ldo, out_mode, 0, nseq, Tq, Tk, H, dh, shift,
+                                c.st, rag_seq(c, nseq, tmp)));
     return prof_end(c, 1);
 }
 
@@ -613,8 +620,8 @@ int attention_b(const Ctx& c, const float* Q, int ldq, const float* K, int ldk, 
 int ss_ld_of(const ModuleW& m) { return m.st.L * m.st.n_ada * 2 * m.st.D; }
 
 // h [nseq*T, D] is updated in place through the L blocks (TransformerBlockDoubleCond / TransformerBlock / InfluenceBlockCross).
-// precision == 1: the GEMM operands xn / att / f1 are written as bf16 by their producers and the weights come from the bf16 twins;
-// the residual stream h, the Q/K/V projections, softmax and all accumulation stay fp32.
+// precision >= 1: the GEMM operands xn / att / f1 are written in the GEMMs' operand type by their producers and the weights come from the
+// low-precision twins; the residual stream h, softmax and all accumulation stay fp32.  Q|K|V take the stack's operand form (Form).
 int run_stack(const Ctx& c, const StackW& w, float* hbuf, const StackRun& r) {
     const Scratch& S = *c.s;
     const int D = w.D, F = w.F, R = (int)c.rows_of(r.nseq, r.T), dh = D / w.H;
@@ -626,92 +633,73 @@ int run_stack(const Ctx& c, const StackW& w, float* hbuf, const StackRun& r) {
     // one GEMM of the stack: fp32 (A fp32, W fp32), bf16 (A bf16 from the producer, W twin) or fp32-split (two fp16 planes each).
     // wtot = elements of the whole weight matrix the twin was made from (its plane stride); the A plane stride is R*K.
     auto gemm = [&](const float* A, int lda, const float* Wf, const void* Wb, size_t woff, size_t wtot, const float* bias, float* C, int ldc, int out_b,
-                    int N, int K, int epi, const float* extra, int ld_extra, Second s2 = Second()) -> int {
-        if (prec == 2) return linear_s(c, A, lda, (size_t)R * K, bw(Wb, woff), w.w_packed ? 0 : K, wtot, bias, C, ldc, (size_t)R * N, out_b == 2, R, N, K, epi, extra, ld_extra, s2);
-        if (bf) return linear_b(c, A, lda, bw(Wb, woff), w.w_packed ? 0 : K, bias, C, ldc, out_b, R, N, K, epi, extra, ld_extra, s2);
+                    int N, int K, int epi, const float* extra, int ld_extra) -> int {
+        if (prec == 2) return linear_s(c, A, lda, (size_t)R * K, bw(Wb, woff), w.w_packed ? 0 : K, wtot, bias, C, ldc, (size_t)R * N, out_b == 2, R, N, K, epi, extra, ld_extra);
+        if (bf) return linear_b(c, A, lda, bw(Wb, woff), w.w_packed ? 0 : K, bias, C, ldc, out_b, R, N, K, epi, extra, ld_extra);
         return linear(c, A, lda, Wf + woff, K, bias, C, ldc, R, N, K, epi, extra, ld_extra);
     };
-    // bf16 path with a head size the plane kernel covers: the projection GEMMs also emit a bf16 copy of Q and K and the scores come from
-    // the bf16 matrix cores (attn_qkp_kernel): 20.1 -> 18.7 ms/step.
-    // fp32-split mode: the projections are written as the two fp16 planes INSTEAD of fp32 rows (same bytes) and the attention works on the planes
-    // throughout (attn_qkp_kernel<DH, 2, true, true>); MMDM_NO_QKP=1 keeps fp32 projections + the fp32 attention kernel, MMDM_QKP=1 selects the
-    // round-2 experiment (extra three-way bf16 copies of Q | K for the scores only: measured slower than the fp32 kernel, 51.6 vs 49.8 ms/step).
-    const bool spa = prec == 2 && (dh == 64 || dh == 128) && !c.h->no_qkp && !c.h->force_qkp;
-    const bool qkp = bf && (prec == 1 || prec == 3 || c.h->force_qkp) && (dh == 64 || dh == 128) && S.qk && !c.h->no_qkp;
-    const int np = prec == 2 ? 3 : 1;
     // precision 3: one fp8 GEMM of the stack.  W8 / Ws: fp8 matrix [rows, K] and its per-output-channel scales, row0 = first output
     // channel used (the K|V slice of the packed cross-attention projection); unit_a: A is the GELU output, stored at the static scale GSCALE
     constexpr float GSCALE = 1.0f;       // (a static x16 on the GELU tensor was measured: its range up to 28 saturates in these networks and doubles the error)
     auto gemm8 = [&](const void* A, bool unit_a, const void* W8, const float* Ws, size_t row0, const float* bias, void* C, int ldc, int out_mode, int N, int K,
-                     int epi, const float* extra, int ld_extra, Second s2 = Second(), bool w_frag = false) -> int {
-        return linear_8(c, A, K, unit_a ? nullptr : S.xs, static_cast<const uint8_t*>(W8) + row0 * K, w_frag ? 0 : K, Ws + row0, bias, C, ldc, out_mode, R, N, K, epi, extra, ld_extra, s2,
+                     int epi, const float* extra, int ld_extra, bool w_frag) -> int {
+        return linear_8(c, A, K, unit_a ? nullptr : S.xs, static_cast<const uint8_t*>(W8) + row0 * K, w_frag ? 0 : K, Ws + row0, bias, C, ldc, out_mode, R, N, K, epi, extra, ld_extra,
                         unit_a ? 1.0f / GSCALE : 1.0f, out_mode == 2 ? GSCALE : 1.0f);
     };
     // AdaLN into the stack GEMMs' operand format: fp32 / bf16 / two fp16 planes, or fp8 + per-row scales
     auto norm = [&](const float* src, const float* ssp, int rows) -> int {
         return ROWOP(c, mmdm_adaln_any, src, ssp, r.ss_ld, rows, S.xn, f8 ? 3 : ob, f8 ? S.xs : nullptr, r.nseq, r.T, D, c.st, row_seq, R);
     };
-    auto second = [&](void* buf, int ld, int cols) { Second s2; if (qkp) { s2.p = buf; s2.ld = ld; s2.cols = cols; s2.plane = (size_t)R * ld; } return s2; };
-    // one-plane (bf16 / fp8) modes: the projection GEMMs' bf16 copy also covers V, and P.V runs on the bf16 matrix cores (attn_qkp_kernel<DH, 1, true>)
-    const bool pvb = qkp && np == 1 && !c.h->no_pvb;
+    // where the projections go: self Q|K|V [R][3D] and cross-attention Q [R][D] in `q`, cross-attention K|V [R][2D] in `kv` -- the bf16 buffers of
+    // Form::BF16, else the fp32 buffers (holding the two fp16 planes in Form::SPLIT)
+    void* const q = w.form == Form::BF16 ? S.qk : S.qkv;
+    void* const kv = w.form == Form::BF16 ? S.kvp : S.kv;
+    // the attention of one block: self (Q, K and V from `q`) or cross (Q from `q`, K and V from `kv`, key sequences shifted by `shift`)
+    auto attend = [&](bool cross, int shift) -> int {
+        const int ldq = cross ? D : 3 * D, ldkv = cross ? 2 * D : 3 * D;
+        if (w.form == Form::F32) {
+            const float* k = cross ? S.kv : S.qkv + D;
+            return attention_b(c, S.qkv, ldq, k, ldkv, k + D, ldkv, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh, shift);
+        }
+        const uint16_t* k = static_cast<const uint16_t*>(cross ? kv : q) + (cross ? 0 : D);
+        return attention_p(c, q, ldq, (size_t)R * ldq, k, ldkv, (size_t)R * ldkv, w.form == Form::SPLIT ? 2 : 1, k + D, ldkv, (size_t)R * ldkv, S.att, D, ob,
+                           r.nseq, r.T, r.T, w.H, dh, shift);
+    };
     for (int l = r.l0; l < w.L; ++l) {
         const LayerW& lw = w.layers[l];
         const LayerWB lb = bf ? w.layers_b[l] : LayerWB();
         auto ss_at = [&](int slot, int row0) { return r.ss + (size_t)row0 * r.ss_ld + ((size_t)l * w.n_ada + slot) * 2 * D; };
+        // output rows [row0, row0 + N) of a packed input projection (self: sa_in, cross: ca_in) into dst [R][N], in the stack's operand form
+        auto project = [&](bool ca, int row0, int N, void* dst) -> int {
+            const float* bias = (ca ? lw.ca_in_b : lw.sa_in_b) + row0;
+            const int out = static_cast<int>(w.form);
+            if (f8) return gemm8(S.xn, false, ca ? lb.ca_in_8 : lb.sa_in_8, ca ? lb.ca_in_s : lb.sa_in_s, row0, bias, dst, N, out, N, D, MMDM_EPI_BIAS, nullptr, 0, w.w_packed);
+            return gemm(S.xn, D, ca ? lw.ca_in_w : lw.sa_in_w, ca ? lb.ca_in_w : lb.sa_in_w, (size_t)row0 * D, (size_t)3 * D * D, bias, static_cast<float*>(dst), N, out, N, D,
+                        MMDM_EPI_BIAS, nullptr, 0);
+        };
         // --- self attention (layers.py:36-45)
         RC(norm(hbuf, ss_at(0, r.sa_row0), r.sa_rows));
-        const int qkld = pvb ? 3 * D : 2 * D;           // row stride of the bf16 copy of the packed projection: Q|K or Q|K|V
-        // all-bf16 attention: nothing reads the fp32 projection, so the GEMM writes bf16 only (a third of the bytes: the fp8 QKV GEMM is output-bound)
-        const _Float16* const qkvh = reinterpret_cast<const _Float16*>(S.qkv);      // spa: planes [2][R][3D] (self) / [2][R][D] (cross-attention queries)
-        const _Float16* const kvh = reinterpret_cast<const _Float16*>(S.kv);        // spa: planes [2][R][2D]
-        if (spa) RC(gemm(S.xn, D, lw.sa_in_w, lb.sa_in_w, 0, (size_t)3 * D * D, lw.sa_in_b, S.qkv, 3 * D, 2, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0));
-        else if (pvb) {
-            if (f8) RC(gemm8(S.xn, false, lb.sa_in_8, lb.sa_in_s, 0, lw.sa_in_b, S.qk, 3 * D, 1, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0, Second(), w.w_packed));
-            else RC(gemm(S.xn, D, lw.sa_in_w, lb.sa_in_w, 0, (size_t)3 * D * D, lw.sa_in_b, static_cast<float*>(S.qk), 3 * D, 1, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0));
-        } else if (f8) RC(gemm8(S.xn, false, lb.sa_in_8, lb.sa_in_s, 0, lw.sa_in_b, S.qkv, 3 * D, 0, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0, second(S.qk, qkld, qkld), w.w_packed));
-        else RC(gemm(S.xn, D, lw.sa_in_w, lb.sa_in_w, 0, (size_t)3 * D * D, lw.sa_in_b, S.qkv, 3 * D, 0, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0, second(S.qk, qkld, qkld)));
-        if (spa) RC(attention_p(c, qkvh, 3 * D, (size_t)R * 3 * D, qkvh + D, 3 * D, (size_t)R * 3 * D, 2, nullptr, 0, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh, 0,
-                                qkvh + 2 * D, 3 * D, (size_t)R * 3 * D));
-        else if (qkp) RC(attention_p(c, S.qk, qkld, (size_t)R * qkld, static_cast<const uint16_t*>(S.qk) + D, qkld, (size_t)R * qkld, np, S.qkv + 2 * D, 3 * D, S.att, D, ob,
-                                r.nseq, r.T, r.T, w.H, dh, 0, pvb ? static_cast<const uint16_t*>(S.qk) + 2 * D : nullptr, qkld));
-        else RC(attention_b(c, S.qkv, 3 * D, S.qkv + D, 3 * D, S.qkv + 2 * D, 3 * D, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh, 0));
+        RC(project(false, 0, 3 * D, q));
+        RC(attend(false, 0));
         if (r.ca_mode) {
             // keys/values of the cross attention come from the layer INPUT of the other stream (or a fixed source):
             // project them before the residual below overwrites h.
-            const float* src = r.ca_mode == 1 ? hbuf : r.kv_src;
-            RC(norm(src, ss_at(2, r.ca_row0), r.ca_rows));
-            const int kvld = pvb ? 2 * D : D;             // bf16 copy of the cross-attention projection: K or K|V
-            if (spa) RC(gemm(S.xn, D, lw.ca_in_w, lb.ca_in_w, (size_t)D * D, (size_t)3 * D * D, lw.ca_in_b + D, S.kv, 2 * D, 2, 2 * D, D, MMDM_EPI_BIAS, nullptr, 0));
-            else if (pvb) {
-                if (f8) RC(gemm8(S.xn, false, lb.ca_in_8, lb.ca_in_s, D, lw.ca_in_b + D, S.kvp, 2 * D, 1, 2 * D, D, MMDM_EPI_BIAS, nullptr, 0, Second(), w.w_packed));
-                else RC(gemm(S.xn, D, lw.ca_in_w, lb.ca_in_w, (size_t)D * D, (size_t)3 * D * D, lw.ca_in_b + D, static_cast<float*>(S.kvp), 2 * D, 1, 2 * D, D, MMDM_EPI_BIAS, nullptr, 0));
-            } else if (f8) RC(gemm8(S.xn, false, lb.ca_in_8, lb.ca_in_s, D, lw.ca_in_b + D, S.kv, 2 * D, 0, 2 * D, D, MMDM_EPI_BIAS, nullptr, 0, second(S.kvp, kvld, kvld), w.w_packed));
-            else RC(gemm(S.xn, D, lw.ca_in_w, lb.ca_in_w, (size_t)D * D, (size_t)3 * D * D, lw.ca_in_b + D, S.kv, 2 * D, 0, 2 * D, D, MMDM_EPI_BIAS, nullptr, 0, second(S.kvp, kvld, kvld)));
+            RC(norm(r.ca_mode == 1 ? hbuf : r.kv_src, ss_at(2, r.ca_row0), r.ca_rows));
+            RC(project(true, D, 2 * D, kv));
         }
-        const int ffn_slot = w.has_ca ? 3 : 1;
-        if (r.ca_mode) RC(gemm(S.att, D, lw.sa_out_w, lb.sa_out_w, 0, (size_t)D * D, lw.sa_out_b, hbuf, D, 0, D, D, MMDM_EPI_BIAS_RESID, hbuf, D));
-        else RC(gemm(S.att, D, lw.sa_out_w, lb.sa_out_w, 0, (size_t)D * D, lw.sa_out_b, hbuf, D, 0, D, D, MMDM_EPI_BIAS_RESID, hbuf, D));
+        RC(gemm(S.att, D, lw.sa_out_w, lb.sa_out_w, 0, (size_t)D * D, lw.sa_out_b, hbuf, D, 0, D, D, MMDM_EPI_BIAS_RESID, hbuf, D));
         // --- cross attention (layers.py:77-88)
         if (r.ca_mode) {
             RC(norm(hbuf, ss_at(1, r.ca_row0), r.ca_rows));
-            if (spa) RC(gemm(S.xn, D, lw.ca_in_w, lb.ca_in_w, 0, (size_t)3 * D * D, lw.ca_in_b, S.qkv, D, 2, D, D, MMDM_EPI_BIAS, nullptr, 0));
-            else if (pvb) {
-                if (f8) RC(gemm8(S.xn, false, lb.ca_in_8, lb.ca_in_s, 0, lw.ca_in_b, S.qk, D, 1, D, D, MMDM_EPI_BIAS, nullptr, 0, Second(), w.w_packed));
-                else RC(gemm(S.xn, D, lw.ca_in_w, lb.ca_in_w, 0, (size_t)3 * D * D, lw.ca_in_b, static_cast<float*>(S.qk), D, 1, D, D, MMDM_EPI_BIAS, nullptr, 0));
-            } else if (f8) RC(gemm8(S.xn, false, lb.ca_in_8, lb.ca_in_s, 0, lw.ca_in_b, S.qkv, D, 0, D, D, MMDM_EPI_BIAS, nullptr, 0, second(S.qk, D, D), w.w_packed));
-            else RC(gemm(S.xn, D, lw.ca_in_w, lb.ca_in_w, 0, (size_t)3 * D * D, lw.ca_in_b, S.qkv, D, 0, D, D, MMDM_EPI_BIAS, nullptr, 0, second(S.qk, D, D)));
-            if (spa) RC(attention_p(c, qkvh, D, (size_t)R * D, kvh, 2 * D, (size_t)R * 2 * D, 2, nullptr, 0, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh,
-                                    r.ca_mode == 1 ? r.nseq / 2 : 0, kvh + D, 2 * D, (size_t)R * 2 * D));
-            else if (qkp) RC(attention_p(c, S.qk, D, (size_t)R * D, S.kvp, pvb ? 2 * D : D, (size_t)R * (pvb ? 2 * D : D), np, S.kv + D, 2 * D, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh,
-                                    r.ca_mode == 1 ? r.nseq / 2 : 0, pvb ? static_cast<const uint16_t*>(S.kvp) + D : nullptr, 2 * D));
-            else RC(attention_b(c, S.qkv, D, S.kv, 2 * D, S.kv + D, 2 * D, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh, r.ca_mode == 1 ? r.nseq / 2 : 0));
+            RC(project(true, 0, D, q));
+            RC(attend(true, r.ca_mode == 1 ? r.nseq / 2 : 0));
             RC(gemm(S.att, D, lw.ca_out_w, lb.ca_out_w, 0, (size_t)D * D, lw.ca_out_b, hbuf, D, 0, D, D, MMDM_EPI_BIAS_RESID, hbuf, D));
         }
         // --- FFN (layers.py:99-106)
-        RC(norm(hbuf, ss_at(ffn_slot, r.ffn_row0), r.ffn_rows));
+        RC(norm(hbuf, ss_at(w.has_ca ? 3 : 1, r.ffn_row0), r.ffn_rows));
         if (f8) {               // FFN on fp8 operands: the GELU output is written as e4m3 at unit scale and read back as the down-projection's A
-            RC(gemm8(S.xn, false, lb.f1_8, lb.f1_s, 0, lw.f1_b, S.f1, F, 2, F, D, MMDM_EPI_BIAS_GELU, nullptr, 0, Second(), w.w_packed));
-            RC(gemm8(S.f1, true, lb.f2_8, lb.f2_s, 0, lw.f2_b, hbuf, D, 0, D, F, MMDM_EPI_BIAS_RESID, hbuf, D, Second(), w.w_packed && F >= 2048));
+            RC(gemm8(S.xn, false, lb.f1_8, lb.f1_s, 0, lw.f1_b, S.f1, F, 2, F, D, MMDM_EPI_BIAS_GELU, nullptr, 0, w.w_packed));
+            RC(gemm8(S.f1, true, lb.f2_8, lb.f2_s, 0, lw.f2_b, hbuf, D, 0, D, F, MMDM_EPI_BIAS_RESID, hbuf, D, w.w_packed && F >= 2048));
         } else {
             RC(gemm(S.xn, D, lw.f1_w, lb.f1_w, 0, (size_t)F * D, lw.f1_b, S.f1, F, ob, F, D, MMDM_EPI_BIAS_GELU, nullptr, 0));
             RC(gemm(S.f1, F, lw.f2_w, lb.f2_w, 0, (size_t)D * F, lw.f2_b, hbuf, D, 0, D, F, MMDM_EPI_BIAS_RESID, hbuf, D));
@@ -746,7 +734,7 @@ int embed(const Ctx& c, const ModuleW& m, const float* xp, int p, float* hdst, i
     if (m.me_s) {
         const _Float16* a = reinterpret_cast<const _Float16*>(xp) + (size_t)p * 2 * rows * NFS;
         return linear_s(c, a, NFS, rows * NFS, m.me_s, c.h->no_pack ? NFS : 0, (size_t)m.st.D * NFS, m.me_b, hdst, m.st.D, 0, 0, (int)rows, m.st.D, NFS, MMDM_EPI_BIAS_PE, pe,
-                        m.st.D, Second(), period);
+                        m.st.D, period);
     }
     return linear(c, xp + (size_t)p * rows * NFP, NFP, m.me_w, NFP, m.me_b, hdst, m.st.D, (int)rows, m.st.D, NFP, MMDM_EPI_BIAS_PE, pe, m.st.D, period, NFP);
 }
@@ -853,7 +841,7 @@ int run_dual_individual(const Ctx& c, const ModuleW& m, const float* x, int xb, 
     return MMDM_OK;
 }
 
-int mixer_core(const Ctx& c, int B, int T, bool dyn_hist) {
+int mixer_core(const Ctx& c, int B, int T) {
     // Everything after the two denoisers: mixermdm.py:691-801 + cfg combine.  n = 2B.
     mmdm_handle H = c.h;
     const int n = 2 * B, Dm = H->mx.st.D;
@@ -910,7 +898,6 @@ int mixer_core(const Ctx& c, int B, int T, bool dyn_hist) {
     else RC(mmdm_blend_cfg_dyn(H->out1, H->out2, H->w23, mode, cf.use_force, cf.force_val, cf.cfg_scale, H->model_out, H->d_hist, lp, B, T, c.st));
     RC(mmdm_hist_copy(H->out1, H->d_hist, 0, nT * NF2, lp, c.st));
     RC(mmdm_hist_copy(H->out2, H->d_hist, 1, nT * NF2, lp, c.st));
-    (void)dyn_hist;
     return MMDM_OK;
 }
 
@@ -974,7 +961,7 @@ int run_step(const Ctx& c) {
                               H->x, H->px1, B, T, NF2, c.st));
         return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
     }
-    RC(mixer_core(c, B, T, true));
+    RC(mixer_core(c, B, T));
     if (c.rag()) RC(mmdm_xstart_ddim_rag(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
                                          H->cfg.xstart_align, c.g->rg, c.st));
     else RC(mmdm_xstart_ddim_f32(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
@@ -1132,6 +1119,8 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     const int npers = so == 1 ? 1 : 2;
     const size_t R = (size_t)npers * n * (T + 1);            // + 1: MDMDenoiser's conditioning token
     const size_t Dx = max2(max2(has_d1 ? D1 : 4, has_d2 ? D : 4), Dm), Fx = max2(max2(has_d1 ? F1 : 4, has_d2 ? F : 4), Fm);
+    // the bf16 projection buffers, in both scratch sets if any stack takes Form::BF16 (sa runs every stack, sb denoiser2 and the second Influence call)
+    const bool bf16_form = h->d1.st.form == Form::BF16 || h->d2.st.form == Form::BF16 || h->mx.st.form == Form::BF16;
     for (Scratch* sc : {&h->sa, &h->sb}) {
         if (sc == &h->sb && !two_models) break;
         const size_t d = sc == &h->sa ? Dx : (size_t)D, f = sc == &h->sa ? Fx : (size_t)F;
@@ -1141,15 +1130,12 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
             (rc = dalloc(h, &sc->qkv, R * 3 * d)) || (rc = dalloc(h, &sc->kv, R * 2 * d)) || (rc = dalloc(h, &sc->f1, R * f * opx / 2)) ||
             (rc = dalloc(h, &sc->xp, (size_t)2 * n * T * (NFS > NFP ? NFS : NFP))))
             return fail(rc);
-        if (c.precision >= 1) {
-            const size_t npl = c.precision == 2 ? 3 : 1;
+        if (bf16_form) {       // bf16 projections: Q|K|V or cross-attention Q [R][3d], cross-attention K|V [R][2d]
             float *q1 = nullptr, *q2 = nullptr;
-            // bf16 [npl][R][2d] (Q|K) and [npl][R][d] (cross-attention K); the one-plane modes also keep V there ([R][3d], [R][2d]): P.V on the bf16 cores
-            const size_t vx = npl == 1 ? 1 : 0;
-            if ((rc = dalloc(h, &q1, npl * R * d + vx * R * d / 2 + 1)) || (rc = dalloc(h, &q2, npl * R * d / 2 + vx * R * d / 2 + 1))) return fail(rc);
+            if ((rc = dalloc(h, &q1, R * 3 * d / 2 + 1)) || (rc = dalloc(h, &q2, R * d + 1))) return fail(rc);
             sc->qk = q1; sc->kvp = q2;
-            if (c.precision == 3 && (rc = dalloc(h, &sc->xs, R))) return fail(rc);
         }
+        if (c.precision == 3 && (rc = dalloc(h, &sc->xs, R))) return fail(rc);
     }
     if (hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork2, hipEventDisableTiming) != hipSuccess ||
@@ -1159,10 +1145,8 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     if (g_serialize_handles.load() < 0) { const char* v = getenv("MMDM_SERIALIZE_HANDLES"); g_serialize_handles.store(v && strcmp(v, "0") != 0 ? 1 : 0); }
     auto env_on = [](const char* k) { const char* v = getenv(k); return v != nullptr && strcmp(v, "0") != 0; };
     if (parent) {       // the switches that decide the FORMAT of the shared weights (and the kernels that read them) are the parent's
-        h->force_qkp = parent->force_qkp; h->no_qkp = parent->no_qkp; h->no_pvb = parent->no_pvb; h->no_pack = parent->no_pack; h->no_split_embed = parent->no_split_embed;
-        h->no_split_cond = parent->no_split_cond;
+        h->no_pack = parent->no_pack; h->no_split_embed = parent->no_split_embed; h->no_split_cond = parent->no_split_cond;
     } else {
-        h->force_qkp = env_on("MMDM_QKP"); h->no_qkp = env_on("MMDM_NO_QKP"); h->no_pvb = env_on("MMDM_NO_BF16_PV");
         h->no_pack = env_on("MMDM_NO_PACK") || env_on("MMDM_SPLIT_NO_PACK");
         h->no_split_embed = env_on("MMDM_NO_SPLIT_EMBED");
         h->no_split_cond = env_on("MMDM_NO_SPLIT_COND");
@@ -1770,7 +1754,7 @@ extern "C" int mmdm_module_forward(mmdm_handle h, int which, const float* x, con
     // (slot 0 of a one-step history); the CFG wrapper returns the combined rows the same kernel leaves in model_out.
     h->hist = mmdm_hist_desc{nullptr, nullptr, nullptr, nullptr, cfgx2 ? nullptr : out, 1, 0};
     if ((rc = push_hist(h, st))) return done(rc);
-    rc = mixer_core(c, nn / 2, T, true);
+    rc = mixer_core(c, nn / 2, T);
     h->hist.mix = nullptr;
     if (!rc) rc = push_hist(h, st);
     if (!rc && cfgx2) {
