@@ -685,6 +685,12 @@ __global__ __launch_bounds__(256, H2 ? 4 : 2) void attn_qkp_kernel(AttnArgs p) {
         const float alpha = EXP2(m_run - m_new);
 #pragma unroll
         for (int r = 0; r < 4; ++r) st[0][r] = EXP2(st[0][r] - m_new);
+        // all-bf16 form: the row sum is taken over the probabilities AS THE MATRIX CORE MULTIPLIES THEM (rounded to bf16, relative error up to 2^-8),
+        // so that the weights of a row sum to one exactly -- a row that one key dominates returns that key's V instead of V x (1 + 2^-8)
+        if constexpr (PVB && !H2) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) st[0][r] = (float)(__bf16)st[0][r];
+        }
         float lsum = ((st[0][0] + st[0][1]) + st[0][2]) + st[0][3];
         lsum = rows_sum(lsum);
         l_run = l_run * alpha + lsum;
@@ -912,7 +918,7 @@ __global__ __launch_bounds__(256, B32_WAVES) void attn_b32_kernel(AttnArgs p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) st[t][r] = EXP2(st[t][r] - m_new);
+            for (int r = 0; r < 4; ++r) st[t][r] = (float)(__bf16)EXP2(st[t][r] - m_new);       // the bf16 value the P.V MFMA multiplies: the row sum below matches it (attn_qkp_kernel)
         float lsum = (((st[0][0] + st[0][1]) + st[0][2]) + st[0][3]) + (((st[1][0] + st[1][1]) + st[1][2]) + st[1][3]);
         lsum = rows_sum(lsum);
         l_run = l_run * alpha + lsum;

@@ -422,10 +422,10 @@ int g_fp8p_grid = 512;          // mmdm_diag_set "fp8p_grid": workgroups of a la
 
 bool mmdm_fp8p_covers(const Fp8pArgs& a) {
     if (!a.A || !a.W || !a.C || !a.w_scale || !a.bias) return false;
-    if ((a.M % 128) || (a.N % 128) || !(a.K == 1024 || a.K == 2048)) return false;
-    const bool ext = a.epilogue == MMDM_EPI_BIAS_RESID || a.epilogue == MMDM_EPI_BIAS_PE;
-    if (ext || a.out_mode == 0) return false;                     // fp32 output (+ residual): FP8P_EXT below
-    if (a.out_mode != 0 && a.epilogue == MMDM_EPI_BIAS_SILU) return false;
+    // exactly what mmdm_fp8p_launch instantiates: K = 1024, bias (+ GELU), a bf16 or fp8 output -- anything else stays on gemm_bf16w_kernel
+    if ((a.M % 128) || (a.N % 128) || a.K != 1024) return false;
+    if (a.epilogue != MMDM_EPI_BIAS && a.epilogue != MMDM_EPI_BIAS_GELU) return false;
+    if (a.out_mode != 1 && a.out_mode != 2) return false;
     if ((long)(a.M / 128) * (a.N / 128) < 512) return false;      // fewer tiles than workgroups: nothing to overlap
     return true;
 }

@@ -596,3 +596,57 @@ def test_small_launch_gemm_on_16x16_chains_is_bitwise_the_production_kernel(M, N
         lib.mmdm_diag_set(b"gemm_s16", -1)
     ref = x.double() @ w.double().T + b.double()
     assert float((ops.linear(x, w, b) .double() - ref).abs().max()) < 2e-5 * (K / 1024) ** 0.5 * 4
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,K", [(12544, 3072, 1024), (12544, 1024, 1024), (12544, 2048, 1024), (12544, 512, 1024), (12500, 1024, 2048), (12544, 1028, 1024)])
+def test_row_split_of_the_fractional_round_is_bitwise_the_single_launch(M, N, K):
+    """The row split that one-stream handles ask for (gemm_f32.hip, `tail`: rows of the whole rounds on the large tile, the remaining rows on a
+    smaller one -- two launches with offset A, C and `extra` pointers), selected here by mmdm_diag_set("gemm_tail", 10) at the stateless entry
+    point.  By the rule's arithmetic every shape below splits (row tiles x column tiles / resident slots: 2352 / 512 -> 85 of 98 row tiles on
+    the large tile; 784 / 512 -> 64 of 98, also at M = 12 500 / K = 2048; N = 2048: 3136 / 768 -> 96 of 98; N = 512: 784 / 768 -> 96 of 98;
+    N = 1028: 882 / 512 -> 56 of 98): asserted from the kernel note (two gemm_pipe launches), and one launch for the PE epilogue, which the
+    rule excludes.  Every epilogue, the residual separate and in place over C, into a NaN-filled output; N = 1028 into a window of a wider
+    buffer (ldc > N) whose other columns must stay NaN.  Bitwise the unsplit launch, and within test_linear_bias's tolerance of float64."""
+    import mixermdm_amd as mm
+    from mixermdm_amd import ops
+    lib, d = mm.load_library(), dev()
+    g = torch.Generator().manual_seed(M + N + K)
+    x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) / K ** 0.5, torch.randn(N, generator=g)
+    r, pe = torch.randn(M, N, generator=g), torch.randn(299, N, generator=g)
+    xd, wd, bd, rd, ped = x.to(d), w.to(d), b.to(d), r.to(d), pe.to(d)
+    ldc = N + 12 if N == 1028 else N                     # 12 floats keep the rows 16-byte aligned
+
+    def run(tail, epi, extra, period=0, in_place=False):
+        lib.mmdm_diag_set(b"gemm_tail", tail)
+        buf = torch.full((M, ldc), float("nan"), device=d)
+        out = buf[:, :N]
+        if in_place:
+            out.copy_(extra)
+            extra = out
+        ops.linear(xd, wd, bd, epi, extra, period, out=out)
+        kern = lib.mmdm_last_gemm_kernel().decode()
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(buf[:, N:]).all()), f"{kern}: wrote beside its {M}x{N} window"
+        return out, kern
+
+    y64 = None
+    try:
+        for epi, extra in [("bias", None), ("gelu", None), ("silu", None), ("sigmoid", None), ("resid", rd), ("resid-in-place", rd)]:
+            ip = epi == "resid-in-place"
+            e = "resid" if ip else epi
+            want, k0 = run(0, e, extra, in_place=ip)
+            got, k1 = run(10, e, extra, in_place=ip)
+            assert k0.count("gemm_pipe<") == 1 and k1.count("gemm_pipe<") == 2 and "+" in k1, (epi, k0, k1)
+            assert torch.isfinite(got).all(), (epi, k1)
+            assert torch.equal(got, want), (epi, k1, float((got - want).abs().max()))
+            if epi in ("bias", "resid", "resid-in-place"):
+                y64 = y64 if y64 is not None else x.double() @ w.double().T + b.double()
+                ref = y64 + r.double() if extra is not None else y64
+                assert_close(got, ref.float(), atol=2e-5 * math.sqrt(max(1.0, K / 1024)), rtol=1e-5, what=f"{M}x{N}x{K} {epi} on {k1}")
+        want, k0 = run(0, "pe", ped, 299)
+        got, k1 = run(10, "pe", ped, 299)
+        assert k1 == k0 and k1.count("gemm_pipe<") == 1, (k0, k1)          # the rule excludes the PE epilogue (row index modulo the period)
+        assert torch.equal(got, want)
+    finally:
+        lib.mmdm_diag_set(b"gemm_tail", -1)

@@ -144,6 +144,48 @@ def test_ragged_batch_items_equal_their_stand_alone_calls(precision, mode):
     s.close()
 
 
+EDGE_LENS = (1, 15, 16, 17, 31, 32, 33, 48, 63, 64)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp32_split", "bf16", "bf16_fp8"])
+def test_ragged_batch_at_the_attention_tile_edges_equals_the_stand_alone_calls(precision):
+    """The 16-bit ragged attention instantiations have no stateless entry point; this is their coverage at the kernels' tile edges: one
+    ragged batch whose items are a partial, a full and a just-over 16-key LDS stage, one / two / three stages (32-key stages for the
+    all-bf16 kernel), the wave (16) and workgroup (64) edges of the queries -- every item bitwise the same item sampled alone, in every
+    precision.  For fp32 the stand-alone calls are held against the oracle as well: one ddim20 step of every length, as (item, person)
+    draws under the file's statistical comparison (tests/parity_tol.py compare_draws, whose bounds are stated for the fp32 modes)."""
+    s = small(max_batch=10, max_frames=64, mode=4, precision=precision)
+    s.set_schedule("ddim20")
+    cond, xs = inputs(EDGE_LENS, seed=11)
+    alone = [s.sample(cond[b:b + 1], x[None])[0] for b, x in enumerate(xs)]
+    items, _, ev = s.sample_ragged_async(cond, xs, EDGE_LENS)
+    ev.synchronize()
+    assert s.rows >= sum(EDGE_LENS)
+    for b, ((o, t), it) in enumerate(zip(s.item_slices(), items)):
+        assert t == EDGE_LENS[b] and torch.isfinite(it).all()
+        assert torch.equal(it, alone[b]), (precision, b, t, (it - alone[b]).abs().max().item())
+    if precision == "fp32":
+        from mixermdm_amd.synthetic import synthetic_state_dict, synthetic_stats
+        sd, st = synthetic_state_dict(seed=7, std=0.05, bias_std=0.02, mixing_mode=4, **DIMS), synthetic_stats()          # the weights of small()
+        W = dict(sd)
+        for k in ("sequence_pos_encoder.pe", "denoiser1.sequence_pos_encoder.pe", "denoiser2.sequence_pos_encoder.pe"):
+            W[k] = pe_table(128)
+        ostats = tuple(torch.as_tensor(st[k]) for k in ("mean_hml", "std_hml", "mean_ih", "std_ih"))
+        mh, sh, mi, si = [v.double().flatten() for v in ostats]
+        denorm = {"pred_xstart": (mh.repeat(2), sh.repeat(2)), "pred_xstart2": (mi.repeat(2), si.repeat(2))}
+        W64, sch, spec = to64(W), OS.make_schedule("cosine", 1000, "ddim20"), MX.MixerSpec(d_heads=2, m_heads=2)
+        steps = []
+        for b, x in enumerate(xs):
+            s.begin(cond[b:b + 1], x[None])
+            s.run(1)
+            got = {k: v.clone().cpu() for k, v in s.state().items() if v is not None}
+            r32, r64 = oracle_step_pair(W, spec, ostats, sch, 3.5, 19, x[None], x[None], cond[b:b + 1], W64=W64)
+            steps.append(({k: got[k] for k in r32}, r32, r64, f"stand-alone T={EDGE_LENS[b]}"))
+        beyond, k, n = compare_draws(steps, "stand-alone steps at the attention tile edges x 2 persons [fp32]", denorm=denorm)
+        assert n == 2 * len(EDGE_LENS)
+    s.close()
+
+
 def test_ragged_single_person_sampler():
     s = small(single_only=True)
     s.set_schedule("ddim20")
