@@ -139,7 +139,8 @@ int mmdm_adaln_f32(const float* h, const float* ss, int ss_ld, int ss_rows, floa
 /* Same with a selectable output type: out_bf16 != 0 writes `out` as bf16 (operand of the next bf16 GEMM). */
 int mmdm_adaln_ex(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_bf16, int nseq, int T, int D, void* stream);
 
-/* Multi-head attention core with add_zero_attn (one extra key, logit 0, value 0), no masks, scale 1/sqrt(dh).
+/* Multi-head attention core with add_zero_attn (one extra key, logit 0, value 0), no masks (mmdm_attention_masked_f32 takes a key-padding
+ * mask), scale 1/sqrt(dh).
  * Q/K/V/O are [nseq, T*, H*dh] views with row strides ld*; the K/V sequence for query sequence s is
  * (s + kv_seq_shift) % nseq (used by the interaction denoiser: person a attends to person b's keys).
  * Replaces the SDPA inside nn.MultiheadAttention  src/models/utils/layers.py:33-44, 74-87. */
@@ -164,6 +165,21 @@ int mmdm_attention_ragged_f32(const float* Q, int ldq, const float* K, int ldk, 
 enum { MMDM_ATTN_NO_ZERO_KEY = 1, MMDM_ATTN_CAUSAL = 2 };
 int mmdm_attention_opts(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* O, int ldo, int out_bf16,
                         int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, void* stream);
+
+/* mmdm_attention_opts with a KEY-PADDING mask (nn.MultiheadAttention's key_padding_mask, inverted): key_valid is a DEVICE byte array
+ * [mask_rows, Tk], 1 = the key exists, 0 = the key is ignored (logit -inf); key sequence kvseq = (s + kv_seq_shift) % nseq reads row
+ * kvseq % mask_rows (mask_rows = 1: one mask for all; mask_rows = the batch size: persons and CFG halves stacked along nseq share their item's
+ * row).  In cross-attention the mask is therefore indexed by the KEY sequence.  The zero key is never masked, so no softmax row is empty: a
+ * query whose keys are all masked gets exactly 0.  Queries at masked positions are computed and written like any other.
+ * key_valid == NULL behaves exactly as mmdm_attention_opts (same kernels, same bits).  The K / V rows of masked keys must be FINITE (their
+ * probability is 0, and 0 * inf is NaN; PyTorch has the same property).  Head sizes 64 / 128 (and the widths padded to them) run a separate
+ * instantiation of the MFMA kernel: with an all-valid mask it gives the bits of the unmasked call, and a mask that keeps the first L keys
+ * gives, in the first L query rows of self-attention, the bits of the unmasked call at T = L.
+ * MMDM_ERR_UNSUPPORTED: a mask together with MMDM_ATTN_NO_ZERO_KEY / MMDM_ATTN_CAUSAL (without the zero key an all-masked first chunk would
+ * form NaN), a mask on a ragged launch.  Replaces key_padding_mask of src/models/utils/layers.py:36-45, 77-88. */
+int mmdm_attention_masked_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* O, int ldo, int out_bf16,
+                              int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const unsigned char* key_valid, int mask_rows,
+                              void* stream);
 
 /* Attention with Q K^T on the bf16 matrix cores: Q and K are given as `nplanes` bf16 planes [plane][rows][ld] (plane strides in elements).
  * nplanes = 3: exact 3-way bf16 splits of the fp32 projections (x = x1 + x2 + x3) -> fp32-accurate scores from six
@@ -197,6 +213,12 @@ int mmdm_cond_silu_f32(const float* time_tab, const int* step_idx, const float* 
  * Replaces src/models/mixermdm.py:691-719 + src/utils/alignment.py:11-158. */
 int mmdm_mixer_pre_f32(const float* o1, const float* o2, const float* stats, float* out1, float* out2,
                        int n, int T, int align, void* stream);
+
+/* mmdm_mixer_pre_f32 with a mask: the alignment's displacement of batch row b ends at frame last_frame[b % last_rows] instead of T - 1
+ * (align_trajectories with a mask: frame lengths - 1, lengths = mask.sum(dim=1)  src/utils/alignment.py:86-91).  last_frame: DEVICE ints in
+ * [0, T) (clamped); NULL = mmdm_mixer_pre_f32.  Everything else -- denormalisation, the rotation round trip, frame 0 -- is unchanged. */
+int mmdm_mixer_pre_masked_f32(const float* o1, const float* o2, const float* stats, float* out1, float* out2,
+                              int n, int T, int align, const int* last_frame, int last_rows, void* stream);
 
 /* Influence head: w[r, 0:nw] = sigmoid(h[r,:] Wout^T + b), nw = 1 or 23; h rows are [rows, D].
  * Replaces Influence.out + sigmoid  src/models/utils/influence.py:124-125. */
@@ -376,6 +398,25 @@ int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S);
 
 /* Check that every weight is present; allocate nothing afterwards. */
 int mmdm_prepare(mmdm_handle h);
+
+/* KEY-PADDING mask of the handle (the reference's `mask` argument: float [n, T, k], valid where mask[..., 0] > 0.5  in2in.py:411-436,
+ * intergen.py:263-274, influence.py:105-117, mixermdm.py:685-708, 735-736).  valid_host: HOST bytes [rows, T], non-zero = the frame exists;
+ * NULL clears the mask (rows / T ignored).  The handle keeps the bytes and, per row, (number of valid frames) - 1 -- the frame
+ * align_trajectories ends its displacement at (alignment.py:86-91; NOT the last valid frame when the mask has holes) -- in device buffers of
+ * its own, sized at mmdm_create; the call waits for this handle's own queued steps (its cached graphs' last replays and the stream of its last mmdm_begin / mmdm_module_forward), not for the device, before it replaces them.  The mask stays in force for mmdm_module_forward and
+ * for mmdm_begin / mmdm_run until it is cleared or replaced:
+ *   - every attention (self, cross, Influence) ignores the masked keys of its key sequence; the alignment uses the per-row frame; PE, AdaLN,
+ *     FFN, the heads, the Influence time mean of modes 1 / 3 (over all T frames, as influence.py:120-121), the normalisers, the blend and the
+ *     DDIM update are unchanged; rows at masked positions are computed and written;
+ *   - mmdm_module_forward which = 0, 1, 2: rows must equal the call's n (the caller repeats the mask for a CFG-doubled batch, as the
+ *     reference's wrappers do: cfg_sampler.py:19-20, 47-48); which = 4 and mmdm_begin / mmdm_run: rows must equal B (the library repeats it for
+ *     its own doubling and for both persons / both models); T must equal the call's T.  A mismatch is MMDM_ERR_ARG at the call;
+ *   - captured step graphs read the mask through the handle's buffers: replacing the VALUES needs no re-capture; masked and unmasked steps
+ *     of the same (B, T, S) are different cache entries and never replay each other.
+ * MMDM_ERR_ARG: rows outside [1, 2 * max_batch], T outside [1, max_frames], a row with no valid frame (the reference would index frame -1).
+ * MMDM_ERR_UNSUPPORTED (never a silent unmasked run): precision 1-3 handles (the 16-bit attention forms take no mask), model1_kind = 1 (the
+ * MDM encoder's src_key_padding_mask), single_only 2 / 3 (and so which = 3); with a mask set, mmdm_begin_ragged is MMDM_ERR_UNSUPPORTED. */
+int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, int T);
 
 /* Begin a sampling call: cond [B, 8*text_dim] (layout src/models/mixermdm.py:342-354) or [B, text_dim] (single_only),
  * x_T [B,T,524] (or [B,T,262]); both chains start from x_T (gaussian_diffusion.py:1863).  Precomputes the text embeddings. */

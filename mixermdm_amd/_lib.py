@@ -7,7 +7,11 @@ _LIB = None
 
 
 class MMDMError(RuntimeError):
-    pass
+    """A non-zero mmdm_status; `status` holds the code (4 = MMDM_ERR_UNSUPPORTED)."""
+
+    def __init__(self, msg, status=0):
+        super().__init__(msg)
+        self.status = int(status)
 
 
 def lib_path():
@@ -64,6 +68,9 @@ SYMBOLS = {
     "mmdm_gaussian_filter1d_f32": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "mmdm_cfg4_ddim_f32": (_I, [_VP, _VP, _I, _VP, C.c_float, C.c_float, C.c_float, _VP, _VP, _I, _I, _I, _VP]),
     "mmdm_attention_opts": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
+    "mmdm_attention_masked_f32": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _I, _VP]),
+    "mmdm_mixer_pre_masked_f32": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP]),
+    "mmdm_set_key_mask": (_I, [_VP, _VP, _I, _I]),
     "mmdm_attention_planes": (_I, [_VP, _I, C.c_int64, _VP, _I, C.c_int64, _I, _VP, _I, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
     "mmdm_attention_bf16": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
     "mmdm_attention_split": (_I, [_VP, _I, C.c_int64, _VP, _I, C.c_int64, _VP, _I, C.c_int64, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP]),
@@ -143,4 +150,4 @@ def check(rc, handle=None):
     msg = msg.decode(errors="replace")
     if "Mixing mode not recognized" in msg or "Mode not recognized" in msg:
         raise ValueError(msg)        # the reference raises ValueError here (mixermdm.py:786, influence.py:90)
-    raise MMDMError(f"[mmdm status {rc}] {msg}")
+    raise MMDMError(f"[mmdm status {rc}] {msg}", rc)

@@ -85,6 +85,9 @@ struct AttnArgs {
     // LONGEST sequence (grid size only); a query tile past its sequence's end leaves at once.
     const int* seq_off; const int* seq_len;
     const int* seq_order; int order_items;      // kernels.h mmdm_rag_seq::order / items (nullptr: sequences in index order)
+    // KEY-PADDING mask (nn.MultiheadAttention key_padding_mask, inverted): bytes [mask_rows][Tk], 1 = the key exists; key sequence kvseq reads row
+    // kvseq % mask_rows.  nullptr = every key exists.  The zero key is never masked, so no softmax row is empty.
+    const unsigned char* key_valid; int mask_rows;
 };
 
 // Which (sequence, head) pair a workgroup works on.  Uniform layout: XCD x owns the contiguous pairs [x ppx, (x + 1) ppx) -- all sequences cost the same.
@@ -193,7 +196,12 @@ __device__ __forceinline__ float rows_sum(float x) {
 // four waves per SIMD stay; two 8-wave workgroups per CU share each K / V stage among twice as many waves and T = 300 gives exactly three
 // rounds of 512 slots) was measured 13 % SLOWER (236 vs 209 us at 64 x 8 x 300 x 128; bit-identical results): four independent
 // workgroups per CU de-synchronise, two 8-wave ones put pairs of lock-stepped waves on every SIMD.  Not instantiated (LAB_NOTES.md).
-template <int DH, bool DIAG = false, int QT = 1, int NW = 4, bool RAG = false>
+// MASK: key-padding mask (AttnArgs::key_valid) -- its own instantiation, so that the unmasked chunk loop holds no trace of it.  A masked key gets
+// the score -inf exactly where a key past Tk does: its probability is 2^-inf = 0 and the running maximum never sees it, so a chunk whose keys
+// are all masked leaves (m, l, O) as they were (alpha = 1, O += 0 * V: K / V rows of masked keys must be FINITE, as for PyTorch).  One byte per
+// lane and chunk (key c0 + lq), requested one chunk ahead -- behind the barrier, in front of the next stage's DMA, so the loop's vmcnt(0) of the
+// next iteration covers it -- and turned into 16 wave-uniform bits by a ballot.
+template <int DH, bool DIAG = false, int QT = 1, int NW = 4, bool RAG = false, bool MASK = false>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_mfma_kernel(AttnArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)          // the buffer-resource type of the LDS-DMA builtin exists in the device pass only
     const int ablate = DIAG ? p.ablate : 0;
@@ -287,9 +295,18 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_mfma_kernel(Att
         const int last_q = min(qt * QBW + QBW - 1, G.Tq - 1);
         nchunks = min(nchunks, last_q / KC + 1);
     }
+    // MASK: this lane's validity byte of a chunk (key c0 + lq; 0 past Tk -- the index is clamped, nothing is read outside the row)
+    const unsigned char* mrow = nullptr;
+    if constexpr (MASK) mrow = p.key_valid + (size_t)(kvseq % p.mask_rows) * G.Tk;
+    auto mask_byte = [&](int c0) -> int {
+        const int key = c0 + lq;
+        const int b = mrow[min(key, G.Tk - 1)];
+        return key < G.Tk ? b : 0;
+    };
 
     // One chunk for the first NA tiles of this wave.  K fragments and V rows are read once and feed every live tile.
-    auto chunk = [&](auto na_c, int c0, const float* Ks, const float* Vs) {
+    // mbyte (MASK only): mask_byte(c0) of this lane.
+    auto chunk = [&](auto na_c, int c0, const float* Ks, const float* Vs, int mbyte) {
         constexpr int NA = decltype(na_c)::value;
         // S^T tiles: st[t][reg] = score(key = c0 + 4g + reg, query = lq of tile t); K fragments double-buffered in registers
         f32x4 st[NA];
@@ -322,6 +339,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_mfma_kernel(Att
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (c0 + 4 * g + r > kmax) st[t][r] = -INFINITY;
+            }
+            if constexpr (MASK) {                       // bit k of the ballot = lane k = key c0 + k
+                const unsigned live = (unsigned)__builtin_amdgcn_ballot_w64(mbyte != 0) >> (4 * g);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (!((live >> r) & 1u)) st[t][r] = -INFINITY;
             }
             if (!(ablate & 4)) {
                 float cmax = vmax3(st[t][0], st[t][1], vmax(st[t][2], st[t][3]));
@@ -407,6 +430,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_mfma_kernel(Att
     // register allocator keeps the state of both alive across the branch (263 registers instead of 184 at DH = 128, QT = 2).
     auto run = [&](auto na_c) {
         constexpr int NA = decltype(na_c)::value;
+        int mb_next = 0;
+        if constexpr (MASK) { if (nchunks > 0) mb_next = mask_byte(0); }
         // the stage index is a compile-time constant (the loop body exists NST times): the K / V fragment reads then address LDS with their
         // per-lane offset + an immediate instead of one VALU add per read (a VALU instruction in this loop costs matrix-pipe time)
         for (int cb = 0; cb < nchunks; cb += NST) {
@@ -423,12 +448,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_mfma_kernel(Att
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (!(ablate & 2)) __builtin_amdgcn_s_barrier();
+            const int mb = mb_next;
+            if constexpr (MASK) { if (ci + 1 < nchunks) mb_next = mask_byte(c0 + KC); }
             if (ci + NST - 1 < nchunks && !(ablate & 1)) stage(c0 + (NST - 1) * KC, stg);
             const float* Ks = smem + cur * STAGE;
             const float* Vs = Ks + KC * DH;
             if (stamps) { if (ci == 0 && tid == 0) stamps[8 * (size_t)bid + 1] = __builtin_amdgcn_s_memrealtime(); t_a = __builtin_amdgcn_s_memrealtime(); }
             // a wave without a live tile (T = 300, QT = 2: wave 3 of the last workgroup) stages its pieces and keeps the barriers, nothing else
-            if constexpr (NA > 0) chunk(na_c, c0, Ks, Vs);
+            if constexpr (NA > 0) chunk(na_c, c0, Ks, Vs, mb);
           }
         }
     };
@@ -1004,7 +1031,9 @@ __global__ void attn_small_kernel(AttnArgs p) {
     const bool nozero = (p.flags & MMDM_ATTN_NO_ZERO_KEY) != 0;
     float m = nozero ? -INFINITY : 0.f, l = nozero ? 0.f : 1.f;
     const int kend = (p.flags & MMDM_ATTN_CAUSAL) ? min(p.Tk, q + 1) : p.Tk;
+    const unsigned char* mrow = p.key_valid ? p.key_valid + (size_t)(kvseq % p.mask_rows) * p.Tk : nullptr;      // key-padding mask: a masked key is skipped
     for (int k = 0; k < kend; ++k) {
+        if (mrow && !mrow[k]) continue;
         const float* kp = p.K + ((size_t)kvseq * p.Tk + k) * p.ldk + head * DH;
         const float* vp = p.V + ((size_t)kvseq * p.Tk + k) * p.ldv + head * DH;
         float s = 0.f;
@@ -1045,7 +1074,9 @@ __global__ __launch_bounds__(256) void attn_wave_kernel(AttnArgs p, int dh) {
     const bool nozero = (p.flags & MMDM_ATTN_NO_ZERO_KEY) != 0;
     float m = nozero ? -INFINITY : 0.f, l = nozero ? 0.f : 1.f;
     const int kend = (p.flags & MMDM_ATTN_CAUSAL) ? min(p.Tk, q + 1) : p.Tk;
+    const unsigned char* mrow = p.key_valid ? p.key_valid + (size_t)(kvseq % p.mask_rows) * p.Tk : nullptr;      // (wave-uniform: one query per wave)
     for (int k = 0; k < kend; ++k) {
+        if (mrow && !mrow[k]) continue;
         const float* kp = p.K + ((size_t)kvseq * p.Tk + k) * p.ldk + head * dh;
         const float* vp = p.V + ((size_t)kvseq * p.Tk + k) * p.ldv + head * dh;
         float sdot = 0.f;
@@ -1083,6 +1114,7 @@ template <int DH>
 int launch_mfma(const AttnArgs& a, hipStream_t st) {
     const dim3 grid(8 * a.pairs_per_xcd * a.qtiles), block(256);
     if (a.seq_off) hipLaunchKernelGGL((attn_mfma_kernel<DH, false, 1, 4, true>), grid, block, attn_smem<DH>(), st, a);
+    else if (a.key_valid) hipLaunchKernelGGL((attn_mfma_kernel<DH, false, 1, 4, false, true>), grid, block, attn_smem<DH>(), st, a);
     else if (a.ablate || a.stamps) hipLaunchKernelGGL((attn_mfma_kernel<DH, true>), grid, block, attn_smem<DH>(), st, a);
     else hipLaunchKernelGGL((attn_mfma_kernel<DH>), grid, block, attn_smem<DH>(), st, a);
     return mmdm_check_launch("attn_mfma");
@@ -1108,6 +1140,8 @@ int mmdm_attn_init(void) {
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_qkp_kernel<64, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, qkp_smem<64, 1>());
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_kernel<128, false, 1, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem<128>());
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_kernel<64, false, 1, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem<64>());
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_kernel<128, false, 1, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem<128>());
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_kernel<64, false, 1, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem<64>());
     if (e != hipSuccess) return mmdm_set_error(MMDM_ERR_HIP, "hipFuncSetAttribute(attn): %s", hipGetErrorString(e));
     return MMDM_OK;
 }
@@ -1127,6 +1161,12 @@ extern "C" int mmdm_attention_opts(const float* Q, int ldq, const float* K, int 
     return mmdm_attention_opts_rag(Q, ldq, K, ldk, V, ldv, Ov, ldo, out_bf16, flags, nseq, Tq, Tk, H, dh, kv_seq_shift, nullptr, stream);
 }
 
+extern "C" int mmdm_attention_masked_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* Ov, int ldo, int out_bf16,
+                                         int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const unsigned char* key_valid, int mask_rows,
+                                         void* stream) {
+    return mmdm_attention_opts_rag(Q, ldq, K, ldk, V, ldv, Ov, ldo, out_bf16, flags, nseq, Tq, Tk, H, dh, kv_seq_shift, nullptr, stream, key_valid, mask_rows);
+}
+
 extern "C" int mmdm_attention_ragged_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                                          int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, int H, int dh, int kv_seq_shift, void* stream) {
     if (!seq_off || !seq_len || max_len <= 0 || total_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_ragged_f32: bad sequence description");
@@ -1136,7 +1176,8 @@ extern "C" int mmdm_attention_ragged_f32(const float* Q, int ldq, const float* K
 
 // rg != nullptr: ragged batch (kernels.h mmdm_rag_seq); Tq = Tk = the longest sequence
 int mmdm_attention_opts_rag(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* Ov, int ldo, int out_bf16,
-                            int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const mmdm_rag_seq* rg, void* stream) {
+                            int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const mmdm_rag_seq* rg, void* stream,
+                            const unsigned char* key_valid, int mask_rows) {
     float* O = static_cast<float*>(Ov);
     if (nseq == 0 || Tq == 0) return MMDM_OK;
     if (int rc = mmdm_kernels_init()) return rc;
@@ -1154,6 +1195,13 @@ int mmdm_attention_opts_rag(const float* Q, int ldq, const float* K, int ldk, co
     a.seq_off = rg ? rg->off : nullptr; a.seq_len = rg ? rg->len : nullptr;
     a.seq_order = (rg && rg->order && rg->items > 0 && nseq % rg->items == 0) ? rg->order : nullptr; a.order_items = rg ? rg->items : 0;
     a.o_plane = (size_t)(rg ? (size_t)rg->total_rows : (size_t)nseq * Tq) * ldo;
+    if (key_valid) {
+        // without the zero key an all-masked first chunk would start the running sums at exp2(-inf - (-inf)) = NaN
+        if (flags) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention with a key mask needs the zero key: MMDM_ATTN_NO_ZERO_KEY / MMDM_ATTN_CAUSAL are not supported with a mask (flags=0x%x)", flags);
+        if (rg) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention with a key mask: ragged batches are not supported (a ragged batch carries its lengths instead)");
+        if (mask_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "attention with a key mask: mask_rows=%d must be positive", mask_rows);
+    }
+    a.key_valid = key_valid; a.mask_rows = key_valid ? mask_rows : 1;
     if (rg && (flags || !(dh == 128 || dh == 64))) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention on ragged batches: head sizes 64 / 128, zero key, no mask (dh=%d flags=0x%x)", dh, flags);
     a.shift = ((kv_seq_shift % nseq) + nseq) % nseq;
     a.qtiles = (Tq + QB - 1) / QB;
@@ -1223,6 +1271,7 @@ int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const voi
     a.Q = nullptr; a.K = nullptr; a.V = V; a.O = static_cast<float*>(Ov); a.ldq = 0; a.ldk = 0; a.ldv = ldv; a.ldo = ldo;
     a.Qp = static_cast<const __bf16*>(Qp); a.Kp = static_cast<const __bf16*>(Kp); a.q_plane = (size_t)q_plane; a.k_plane = (size_t)k_plane; a.ldqp = ldq; a.ldkp = ldk;
     a.Vp = static_cast<const __bf16*>(Vp); a.ldvp = ldvp; a.v_plane = (size_t)v_plane;
+    a.key_valid = nullptr; a.mask_rows = 1;              // the 16-bit forms take no key mask
     if (Vp && (nplanes == 3 || (reinterpret_cast<uintptr_t>(Vp) & 15) || (ldvp & 7) || ldvp < H * dh || (nplanes == 2 && (v_plane & 7))))
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_planes: 16-bit V needs one (bf16) or two (fp16 split) planes, 16-byte aligned rows / planes and a row stride >= H*dh");
     a.nseq = nseq; a.Tq = Tq; a.Tk = Tk; a.H = H; a.out_bf16 = out_mode; a.flags = flags; a.dh = dh; a.ablate = g_attn_ablate; a.stamps = g_attn_stamps;

@@ -93,10 +93,12 @@ __device__ __forceinline__ void rot6d_roundtrip(const float d[6], float out[6]) 
 // frame 0 / the last frame of its item come from the row maps; padding rows leave at once.  The arithmetic is the uniform kernel's.
 template <bool RAG>
 __global__ __launch_bounds__(256) void mixer_pre_kernel(const float* __restrict__ o1, const float* __restrict__ o2, const float* __restrict__ stats,
-                                                         float* __restrict__ out1, float* __restrict__ out2, int n, int T, int align, mmdm_rag rg) {
+                                                         float* __restrict__ out1, float* __restrict__ out2, int n, int T, int align, mmdm_rag rg,
+                                                         const int* __restrict__ last_frame, int last_rows) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     int j, t, p;
     size_t seq;
+    int tl;                                   // end frame of the alignment's displacement
     if constexpr (RAG) {
         if (idx >= n * rg.rows * 2 * NJ) return;
         j = idx % NJ;
@@ -106,6 +108,7 @@ __global__ __launch_bounds__(256) void mixer_pre_kernel(const float* __restrict_
         t = rg.row_pos[rl];
         T = rg.item_len[item];
         seq = (size_t)(r - t) * NF2 + (size_t)p * NF;
+        tl = T - 1;
     } else {
         const int total = n * 2 * T * NJ;
         if (idx >= total) return;
@@ -114,6 +117,8 @@ __global__ __launch_bounds__(256) void mixer_pre_kernel(const float* __restrict_
         p = (idx / (NJ * T)) % 2;
         const int b = idx / (NJ * T * 2);
         seq = (size_t)b * T * NF2 + (size_t)p * NF;      // start of (b, frame 0, person p)
+        // mask given: frame lengths - 1 with lengths = mask.sum(dim=1) (alignment.py:89-91) -- the COUNT of valid frames, not the last valid one
+        tl = last_frame ? min(max(last_frame[b % last_rows], 0), T - 1) : T - 1;
     }
     const float* mh = stats, *sh = stats + NF, *mi = stats + 2 * NF, *si = stats + 3 * NF;
     const size_t off = seq + (size_t)t * NF2;
@@ -155,9 +160,9 @@ __global__ __launch_bounds__(256) void mixer_pre_kernel(const float* __restrict_
     if (align) {
         // align_motions(motion1 = interaction person (target), motion2 = individual person (moved))  alignment.py:112-158
         const float* a0 = o1 + seq;                               // frame 0
-        const float* aL = o1 + seq + (size_t)(T - 1) * NF2;       // last frame (mask=None: alignment.py:86-88)
+        const float* aL = o1 + seq + (size_t)tl * NF2;            // last frame (mask=None: alignment.py:86-88), or the mask's frame count - 1
         const float* c0 = o2 + seq;
-        const float* cL = o2 + seq + (size_t)(T - 1) * NF2;
+        const float* cL = o2 + seq + (size_t)tl * NF2;
         const V3 p1_0{c0[0] * si[0] + mi[0], c0[1] * si[1] + mi[1], c0[2] * si[2] + mi[2]};
         const V3 p1_L{cL[0] * si[0] + mi[0], cL[1] * si[1] + mi[1], cL[2] * si[2] + mi[2]};
         const V3 p2_0{a0[0] * sh[0] + mh[0], a0[1] * sh[1] + mh[1], a0[2] * sh[2] + mh[2]};
@@ -469,14 +474,29 @@ extern "C" int mmdm_mixer_pre_f32(const float* o1, const float* o2, const float*
     if (n == 0 || T == 0) return MMDM_OK;
     if (!o1 || !o2 || !stats || !out1 || !out2 || n < 0 || T < 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_mixer_pre_f32: bad arguments");
     const int total = n * 2 * T * MMDM_NJ;
-    hipLaunchKernelGGL(mixer_pre_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), o1, o2, stats, out1, out2, n, T, align, mmdm_rag{});
+    hipLaunchKernelGGL(mixer_pre_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), o1, o2, stats, out1, out2, n, T, align, mmdm_rag{},
+                       (const int*)nullptr, 1);
     return mmdm_check_launch("mixer_pre");
+}
+
+int mmdm_mixer_pre_last(const float* o1, const float* o2, const float* stats, float* out1, float* out2, int n, int T, int align,
+                        const int* last_frame, int last_rows, hipStream_t st) {
+    if (n == 0 || T == 0) return MMDM_OK;
+    if (!o1 || !o2 || !stats || !out1 || !out2 || n < 0 || T < 0 || (last_frame && last_rows <= 0)) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_mixer_pre_masked_f32: bad arguments");
+    const int total = n * 2 * T * MMDM_NJ;
+    hipLaunchKernelGGL(mixer_pre_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, o1, o2, stats, out1, out2, n, T, align, mmdm_rag{}, last_frame, last_frame ? last_rows : 1);
+    return mmdm_check_launch("mixer_pre");
+}
+
+extern "C" int mmdm_mixer_pre_masked_f32(const float* o1, const float* o2, const float* stats, float* out1, float* out2,
+                                         int n, int T, int align, const int* last_frame, int last_rows, void* stream) {
+    return mmdm_mixer_pre_last(o1, o2, stats, out1, out2, n, T, align, last_frame, last_rows, static_cast<hipStream_t>(stream));
 }
 
 // ragged batch: `groups` groups of rg.rows frame rows (the cond | uncond halves of the CFG-doubled batch)
 int mmdm_mixer_pre_rag(const float* o1, const float* o2, const float* stats, float* out1, float* out2, int groups, int align, const mmdm_rag& rg, hipStream_t st) {
     const int total = groups * rg.rows * 2 * MMDM_NJ;
-    hipLaunchKernelGGL(mixer_pre_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, o1, o2, stats, out1, out2, groups, 0, align, rg);
+    hipLaunchKernelGGL(mixer_pre_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, o1, o2, stats, out1, out2, groups, 0, align, rg, (const int*)nullptr, 1);
     return mmdm_check_launch("mixer_pre_rag");
 }
 

@@ -159,4 +159,8 @@ int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const voi
                              const void* Vp, int ldvp, int64_t v_plane, void* O, int ldo, int out_mode, int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, void* stream,
                              const mmdm_rag_seq* rg = nullptr);
 int mmdm_attention_opts_rag(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* O, int ldo, int out_bf16,
-                            int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const mmdm_rag_seq* rg, void* stream);
+                            int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const mmdm_rag_seq* rg, void* stream,
+                            const unsigned char* key_valid = nullptr, int mask_rows = 0);
+// mmdm_mixer_pre_f32 with the alignment's end frame per sequence (geometry.hip): last_frame [last_rows] DEVICE ints, batch row b reads entry b % last_rows
+int mmdm_mixer_pre_last(const float* o1, const float* o2, const float* stats, float* out1, float* out2, int n, int T, int align,
+                        const int* last_frame, int last_rows, hipStream_t st);

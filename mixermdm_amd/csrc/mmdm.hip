@@ -276,13 +276,18 @@ struct mmdm_handle_s {
     // history: host mirror + the device-side descriptor the step's kernels read (kernels.h: mmdm_hist_desc)
     mmdm_hist_desc hist = {nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0};
     mmdm_hist_desc* d_hist = nullptr;
+    // key-padding mask (mmdm_set_key_mask): handle-owned device buffers sized at mmdm_create, read by the attention and alignment kernels at run
+    // time -- a captured step graph bakes in the ADDRESSES (and so whether a mask is set: part of the graph key), never the values
+    unsigned char* d_kmask = nullptr;       // [2 * max_batch, max_frames] bytes, rows of mask_T: 1 = the key exists
+    int* d_klast = nullptr;                 // [2 * max_batch] valid frames of a row - 1 (align_trajectories: lengths - 1)
+    int mask_rows = 0, mask_T = 0;          // 0 rows: no mask set
     hipStream_t call_stream = nullptr;      // stream of the last mmdm_begin: mmdm_set_history orders its descriptor update on it
 
     // Captured step graphs, least-recently-used cache keyed by everything a captured node bakes in: (B, T, S).  History
     // destinations, schedule tables, conditioning and the step index are device-side data, not node arguments, so the eval
     // caller's alternating (B, T) requests (src/evaluation/datasets.py:101-122, 438) replay cached graphs instead of re-capturing.
     // (ragged calls: T = query tiles of the longest item, rows = the group stride; uniform calls: rows = 0)
-    struct GraphEntry { int B, T, S, rows; hipGraphExec_t exec; uint64_t used; hipEvent_t done; };      // done: recorded behind the entry's last replay
+    struct GraphEntry { int B, T, S, rows; hipGraphExec_t exec; uint64_t used; hipEvent_t done; int masked; };      // done: recorded behind the entry's last replay
     std::vector<GraphEntry> graphs;
     size_t graph_cap = 8;
     uint64_t graph_clock = 0;
@@ -490,6 +495,10 @@ struct Ctx {
     hipStream_t st;
     const Scratch* s;
     const Geom* g = nullptr;      // row geometry (nullptr: uniform, sizes as passed)
+    // key-padding mask in force (mmdm_set_key_mask): the handle's byte mask and per-row last-frame index, row = sequence % kmask_rows
+    const unsigned char* kmask = nullptr;
+    const int* klast = nullptr;
+    int kmask_rows = 0;
     bool rag() const { return g && g->rag; }
     size_t rows_of(int nseq, int T) const { return g ? g->rows_of(nseq) : (size_t)nseq * T; }
 };
@@ -613,7 +622,7 @@ int attention_b(const Ctx& c, const float* Q, int ldq, const float* K, int ldk, 
                 int nseq, int Tq, int Tk, int H, int dh, int shift) {
     mmdm_rag_seq tmp;
     RC(prof_begin(c, 1, attn_flops(c, nseq, H, Tq, Tk, dh), attn_bytes(c, nseq, H, Tq, Tk, dh)));
-    RC(mmdm_attention_opts_rag(Q, ldq, K, ldk, V, ldv, O, ldo, out_bf16, 0, nseq, Tq, Tk, H, dh, shift, rag_seq(c, nseq, tmp), c.st));
+    RC(mmdm_attention_opts_rag(Q, ldq, K, ldk, V, ldv, O, ldo, out_bf16, 0, nseq, Tq, Tk, H, dh, shift, rag_seq(c, nseq, tmp), c.st, c.kmask, c.kmask_rows));
     return prof_end(c, 1);
 }
 
@@ -657,6 +666,7 @@ int run_stack(const Ctx& c, const StackW& w, float* hbuf, const StackRun& r) {
     // the attention of one block: self (Q, K and V from `q`) or cross (Q from `q`, K and V from `kv`, key sequences shifted by `shift`)
     auto attend = [&](bool cross, int shift) -> int {
         const int ldq = cross ? D : 3 * D, ldkv = cross ? 2 * D : 3 * D;
+        if (c.kmask && w.form != Form::F32) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "key mask: the 16-bit attention forms (precision 1-3) take no mask");
         if (w.form == Form::F32) {
             const float* k = cross ? S.kv : S.qkv + D;
             return attention_b(c, S.qkv, ldq, k, ldkv, k + D, ldkv, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh, shift);
@@ -849,6 +859,7 @@ int mixer_core(const Ctx& c, int B, int T) {
     const bool rag = c.rag();
     const size_t nT = c.rows_of(n, T);               // frame rows of the CFG-doubled batch (uniform: n * T)
     if (rag) RC(mmdm_mixer_pre_rag(H->o1, H->o2, H->d_stats, H->out1, H->out2, n / B, cf.align, c.g->rg, c.st));
+    else if (c.klast) RC(mmdm_mixer_pre_last(H->o1, H->o2, H->d_stats, H->out1, H->out2, n, T, cf.align, c.klast, c.kmask_rows, c.st));
     else RC(mmdm_mixer_pre_f32(H->o1, H->o2, H->d_stats, H->out1, H->out2, n, T, cf.align, c.st));
     // motion_embed + PE of the four streams (mixermdm.py:722-732); seq = p*n + b
     RC(repack(c, H->mx, H->out1, NF2, H->sa.xp, 2, (int)nT));
@@ -866,7 +877,7 @@ int mixer_core(const Ctx& c, int B, int T) {
     }
     if (split) {
         // the two Influence calls (mixermdm.py:735-736: person 1, person 2) are independent: one per stream (64.7 -> 64.2 ms/step)
-        Ctx c2{H, H->st2, &H->sb, c.g};
+        Ctx c2{H, H->st2, &H->sb, c.g, c.kmask, c.klast, c.kmask_rows};
         StackRun r1 = r, r2 = r;
         r1.nseq = r2.nseq = n;
         r1.sa_rows = r2.sa_rows = n;
@@ -939,7 +950,7 @@ int run_step(const Ctx& c) {
     if (H->overlap && !H->prof.on) {
         // fork: denoiser2 (with its AdaLN-projection GEMM) on the auxiliary stream with its own scratch; denoiser1 and the mixer's
         // projections on the caller's stream (denoiser1 is the shorter model); join before the mixer
-        Ctx c2{H, H->st2, &H->sb, c.g};
+        Ctx c2{H, H->st2, &H->sb, c.g, c.kmask, c.klast, c.kmask_rows};
         HIPCHK(hipEventRecord(H->ev_fork, c.st));
         HIPCHK(hipStreamWaitEvent(H->st2, H->ev_fork, 0));
         RC(cond_vectors(c2, H->d2, H->txt_d2, H->se_d2, H->ss_d2, 3 * n));
@@ -1038,6 +1049,16 @@ struct ProfPause {
 };
 
 int push_hist(mmdm_handle h, hipStream_t st) { return mmdm_set_hist_desc(h->d_hist, h->hist, st); }
+
+// The handle's key mask for a call over `rows` mask rows of T frames: checks the row-count rule of the caller and points the context at the
+// handle-owned buffers.  No mask set: the context stays as it is (today's path).
+int use_key_mask(mmdm_handle h, Ctx& c, int rows, int T, const char* who) {
+    if (!h->mask_rows) return MMDM_OK;
+    if (h->mask_rows != rows || h->mask_T != T)
+        return mmdm_set_error(MMDM_ERR_ARG, "%s: the key mask set on the handle is [%d, %d], this call needs [%d, %d] (mmdm_set_key_mask)", who, h->mask_rows, h->mask_T, rows, T);
+    c.kmask = h->d_kmask; c.klast = h->d_klast; c.kmask_rows = rows;
+    return MMDM_OK;
+}
 
 }  // namespace
 
@@ -1186,6 +1207,13 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     h->d_hist = reinterpret_cast<mmdm_hist_desc*>(tmp);
     if (hipMemcpy(h->d_hist, &h->hist, sizeof(mmdm_hist_desc), hipMemcpyHostToDevice) != hipSuccess)
         return fail(mmdm_set_error(MMDM_ERR_HIP, "mmdm_create: history descriptor upload failed"));
+    {       // key-mask buffers (mmdm_set_key_mask): up to 2 * max_batch rows (a CFG-doubled batch handed to mmdm_module_forward)
+        const size_t mrows = (size_t)2 * B;
+        if ((rc = dalloc(h, &tmp, (mrows * T + 3) / 4))) return fail(rc);
+        h->d_kmask = reinterpret_cast<unsigned char*>(tmp);
+        if ((rc = dalloc(h, &tmp, mrows))) return fail(rc);
+        h->d_klast = reinterpret_cast<int*>(tmp);
+    }
     if (const char* e = getenv("MMDM_GRAPH_CACHE")) { long v = atol(e); if (v >= 1 && v <= 64) h->graph_cap = (size_t)v; }
     // ragged calls (mmdm_begin_ragged): row maps for up to 4 groups of max_batch * max_frames rows, and per module the PE rows of a group
     if (so <= 1 && !mdm) {
@@ -1415,6 +1443,8 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     if (!h || !cond || !x_T) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_begin: null argument");
     if (!h->prepared || h->S == 0) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_begin: prepare() and set_schedule() first"));
     Geom g;
+    if (lens && h->mask_rows)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: a key mask is set on the handle; ragged batches carry their lengths instead (clear it with mmdm_set_key_mask(h, NULL, 0, 0))"));
     if (lens) {
         if (h->cfg.single_only > 1 || h->d1.kind == 1 || !h->d_rag)
             return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: ragged batches cover the two-chain MixerMDM sampler and the single-person sampler over in2IN / InterGen denoisers"));
@@ -1442,6 +1472,8 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
         if (B <= 0 || B > h->cfg.max_batch || T <= 0 || T > h->cfg.max_frames)
             return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_begin: B=%d T=%d exceed the handle's max_batch=%d / max_frames=%d", B, T, h->cfg.max_batch, h->cfg.max_frames));
         g.rows = B * T; g.real_rows = B * T; g.tt1 = (double)B * T * (T + 1);
+        Ctx probe{h, nullptr, &h->sa};
+        RC(herr(h, use_key_mask(h, probe, B, T, "mmdm_begin")));
     }
     g.B = B; g.T = T;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1539,6 +1571,9 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
         return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_run: %d steps requested, %d left in the schedule", nsteps, h->host_step + 1));
     hipStream_t st = static_cast<hipStream_t>(stream);
     Ctx c{h, st, &h->sa, &h->geom};
+    if (h->mask_rows && h->geom.rag) return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_run: a key mask is set on the handle and the begun call is ragged"));
+    RC(herr(h, use_key_mask(h, c, h->B, h->T, "mmdm_run")));
+    const int masked = c.kmask ? 1 : 0;
     if (use_graph && !h->prof.on && !st) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_run: graph capture needs a non-default stream"));
     if (nsteps == 0) return MMDM_OK;
     // MMDM_SERIALIZE_HANDLES=1: this call's steps start behind the previous sampling call of any handle, and the next one behind them
@@ -1563,7 +1598,7 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
         // what a captured node bakes in: uniform (B, T, S); ragged (B, query tiles of the longest item, S, group stride) -- the lengths are device data
         const int kT = h->geom.rag ? (h->T + 63) / 64 : h->T, kR = h->geom.rag ? h->geom.rows : 0;
         for (auto& g : h->graphs)
-            if (g.B == h->B && g.T == kT && g.S == h->S && g.rows == kR) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
+            if (g.B == h->B && g.T == kT && g.S == h->S && g.rows == kR && g.masked == masked) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
         if (!exec) {
             hipGraph_t g = nullptr;
             // one capture at a time in the process: several handles may be driven from several host threads (mmdm_create_shared), and two
@@ -1597,7 +1632,7 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
                 (void)hipGraphExecDestroy(exec);
                 return herr(h, mmdm_set_error(MMDM_ERR_HIP, "mmdm_run: hipEventCreate: %s", hipGetErrorString(e)));
             }
-            h->graphs.push_back({h->B, kT, h->S, kR, exec, ++h->graph_clock, done});
+            h->graphs.push_back({h->B, kT, h->S, kR, exec, ++h->graph_clock, done, masked});
             ++h->n_captures;
             // the FIRST launch of a fresh exec binds the runtime's internal branch streams to it (hip::Graph::UpdateStreams): still inside the
             // exclusive section -- beside another thread's launch that is where the runtime was seen to crash
@@ -1664,6 +1699,9 @@ extern "C" int mmdm_module_forward(mmdm_handle h, int which, const float* x, con
     if (which < 0 || which > 4 || (so_ == 1 && which != 0) || (so_ == 2 && which != 1) || (so_ == 3 && (which == 2 || which == 0)) || (so_ != 3 && which == 3)) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_module_forward: bad module %d", which));
     hipStream_t st = static_cast<hipStream_t>(stream);
     Ctx c{h, st, &h->sa};
+    if (h->mask_rows && which == 3) return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_module_forward: module 3 (dual_individual) takes no key mask"));
+    RC(herr(h, use_key_mask(h, c, n, T, "mmdm_module_forward")));
+    h->call_stream = st;                    // mmdm_set_key_mask waits for this stream before it replaces the mask      // which 0, 1, 2: the caller's (doubled) n rows; which 4: B rows, repeated by the % of the kernels
     const int td = h->cfg.text_dim;
     ProfPause pause(h->prof);
     TailScope tail_scope((so_ == 1 || so_ == 2) ? 10 : 0);
@@ -1762,6 +1800,43 @@ extern "C" int mmdm_module_forward(mmdm_handle h, int which, const float* x, con
         if (e != hipSuccess) rc = mmdm_set_error(MMDM_ERR_HIP, "mmdm_module_forward: %s", hipGetErrorString(e));
     }
     return done(rc);
+}
+
+extern "C" int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, int T) {
+    if (!h) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_key_mask: null handle");
+    if (!valid_host) { h->mask_rows = 0; h->mask_T = 0; return MMDM_OK; }
+    if (h->cfg.precision != 0)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: precision %d handle -- the 16-bit attention forms take no key mask (precision 0 only)", h->cfg.precision));
+    if (h->cfg.single_only != 2 && h->d1.kind == 1)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: model1_kind = 1 -- the MDM encoder's src_key_padding_mask is not implemented"));
+    if (h->cfg.single_only >= 2)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: single_only = %d -- the 4-way CFG and dual samplers take no key mask", h->cfg.single_only));
+    if (rows <= 0 || rows > 2 * h->cfg.max_batch || T <= 0 || T > h->cfg.max_frames)
+        return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_key_mask: mask [%d, %d] outside the handle's [1 .. 2 * max_batch = %d, 1 .. max_frames = %d]", rows, T, 2 * h->cfg.max_batch, h->cfg.max_frames));
+    std::vector<unsigned char> bytes((size_t)rows * T);
+    std::vector<int> last(rows);
+    for (int r = 0; r < rows; ++r) {
+        int cnt = 0;
+        for (int t = 0; t < T; ++t) { const unsigned char v = valid_host[(size_t)r * T + t] ? 1 : 0; bytes[(size_t)r * T + t] = v; cnt += v; }
+        if (cnt == 0) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_key_mask: row %d has no valid frame (the reference would index frame -1: alignment.py:89-91)", r));
+        last[r] = cnt - 1;
+    }
+    // The buffers may be read by steps of THIS handle that are still queued: wait for them only -- the event behind each cached graph's last
+    // replay and the stream of the handle's last call (eager steps and module forwards; the auxiliary stream joins it) -- never for the
+    // device, which would stall other handles' streams.  Copies go through that stream; the shared lock keeps a capture of another handle
+    // (exclusive section of mmdm_run) apart from the waits and copies, as for graph launches.
+    {
+        std::shared_lock<std::shared_mutex> lock(g_graph_mu);
+        for (auto& g : h->graphs)
+            if (g.done) HIPCHK(hipEventSynchronize(g.done));
+        hipStream_t st = h->call_stream;
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(h->d_kmask, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(h->d_klast, last.data(), last.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));          // the host vectors are transient
+    }
+    h->mask_rows = rows; h->mask_T = T;
+    return MMDM_OK;
 }
 
 extern "C" int mmdm_graph_parked(void) {

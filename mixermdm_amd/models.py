@@ -44,6 +44,43 @@ def _holder_tree(root, name, tensor):
     mod.register_parameter(parts[-1], nn.Parameter(tensor, requires_grad=False))
 
 
+def key_valid_of(mask):
+    """The reference's `mask` argument (float [n, T, k]; only mask[..., 0] is used) -> bool [n, T], True = the frame exists
+    (key_padding_mask = ~(mask[..., 0] > 0.5): in2in.py:411-436, influence.py:105-117)."""
+    if mask.dim() != 3:
+        raise ValueError(f"mask: [n, T, k] expected, got {tuple(mask.shape)}")
+    return mask[..., 0] > 0.5
+
+
+class _KeyMask:
+    """Sets the key mask on a sampler's handle for the duration of one call and clears it afterwards; the cases the library refuses
+    (MMDM_ERR_UNSUPPORTED from mmdm_set_key_mask or from the masked call itself) raise NotImplementedError with the library's message.
+    mask=None: nothing is touched."""
+    UNSUPPORTED = 4
+
+    def __init__(self, smp, mask):
+        self.smp, self.mask = smp, mask
+
+    def __enter__(self):
+        if self.mask is not None:
+            from ._lib import MMDMError
+            try:
+                self.smp.set_key_mask(key_valid_of(self.mask))
+            except MMDMError as e:
+                if e.status == self.UNSUPPORTED:
+                    raise NotImplementedError(str(e)) from None
+                raise
+        return self.smp
+
+    def __exit__(self, etype, exc, tb):
+        if self.mask is not None:
+            from ._lib import MMDMError
+            self.smp.set_key_mask(None)
+            if isinstance(exc, MMDMError) and exc.status == self.UNSUPPORTED:
+                raise NotImplementedError(str(exc)) from None
+        return False
+
+
 class _Callable(nn.Module):
     """Base of the inner callables: shares the owner's sampler."""
 
@@ -68,13 +105,12 @@ class DenoiserHandle(_Callable):
         self.text_dim = 768
 
     def forward(self, x, timesteps, mask=None, cond=None):
-        if mask is not None:
-            raise NotImplementedError("key_padding masks are not used on the inference path (mask=None: mixermdm.py:533)")
         n = x.shape[0]
         if n % 2:
             raise ValueError("the HIP denoiser works on the CFG-doubled batch (even number of rows)")
         smp = self._owner._sampler_for(n // 2, x.shape[1])
-        return smp.module_forward(self.which, x, cond, self._uniform_t(timesteps))
+        with _KeyMask(smp, mask):
+            return smp.module_forward(self.which, x, cond, self._uniform_t(timesteps))
 
 
 class Mixer(_Callable):
@@ -91,12 +127,11 @@ class Mixer(_Callable):
         self.history_out1, self.history_out2, self.history_out_influenced = [], [], []
 
     def forward(self, x1, timesteps, cond=None, mask=None, x2=None):
-        if mask is not None:
-            raise NotImplementedError("mask must be None on the inference path")
         if self.mixing_mode not in (1, 2, 3, 4):
             raise ValueError("Mixing mode not recognized")
         smp = self._owner._sampler_for(x1.shape[0] // 2, x1.shape[1])
-        return smp.module_forward(2, x1, cond, self._uniform_t(timesteps), x2=x2)
+        with _KeyMask(smp, mask):
+            return smp.module_forward(2, x1, cond, self._uniform_t(timesteps), x2=x2)
 
 
 class ClassifierFreeSampleModelX2(nn.Module):
@@ -110,8 +145,6 @@ class ClassifierFreeSampleModelX2(nn.Module):
         self.s = cfg_scale
 
     def forward(self, x, x2, timesteps, cond=None, mask=None):
-        if mask is not None:
-            raise NotImplementedError("mask must be None on the inference path")
         if cond is None:
             raise NotImplementedError("the HIP mixer is text-conditioned: cond [B, 8*768] is required (mixermdm.py:342-354)")
         mixer = self.model
@@ -119,7 +152,8 @@ class ClassifierFreeSampleModelX2(nn.Module):
             raise ValueError("Mixing mode not recognized")
         owner = mixer._owner
         smp = owner._sampler_for(x.shape[0], x.shape[1], cfg_scale=self.s)
-        return smp.module_forward(4, x, cond, _Callable._uniform_t(timesteps), x2=x2)
+        with _KeyMask(smp, mask):             # B rows: the library repeats the mask for its own doubling (cfg_sampler.py:47-48)
+            return smp.module_forward(4, x, cond, _Callable._uniform_t(timesteps), x2=x2)
 
 
 class MixerDiffusion:
@@ -143,13 +177,12 @@ class MixerDiffusion:
         mixer = model.model if isinstance(model, ClassifierFreeSampleModelX2) else model
         owner = mixer._owner
         model_kwargs = model_kwargs or {}
-        if model_kwargs.get("mask") is not None:
-            raise NotImplementedError("mask must be None")
+        mask = model_kwargs.get("mask")      # handed to the model unchanged at every step (gaussian_diffusion.py:1871-1899): set once on the handle
         cond = model_kwargs["cond"]
         B, T, _ = shape
         dev = owner.device
         x_T = noise if noise is not None else torch.randn(*shape, device=dev)
-        return owner._run_loop(self, cond, x_T, cfg_scale=getattr(model, "s", owner.cfg_mixing_weight))
+        return owner._run_loop(self, cond, x_T, cfg_scale=getattr(model, "s", owner.cfg_mixing_weight), mask=mask)
 
 
 class MixerMDM(nn.Module):
@@ -338,9 +371,14 @@ class MixerMDM(nn.Module):
         return self.text_encoder(batch)
 
     # ---- sampling -----------------------------------------------------------------------------------
-    def _run_loop(self, diffusion, cond, x_T, cfg_scale=None):
+    def _run_loop(self, diffusion, cond, x_T, cfg_scale=None, mask=None):
         B, T = x_T.shape[:2]
         smp = self._sampler_for(B, T, cfg_scale=cfg_scale)
+        with _KeyMask(smp, mask):
+            return self._run_loop_on(smp, diffusion, cond, x_T)
+
+    def _run_loop_on(self, smp, diffusion, cond, x_T):
+        B, T = x_T.shape[:2]
         sch = diffusion.schedule
         # the facade builds a new MixerDiffusion per call (as the reference does, mixermdm.py:515-522): compare schedules by CONTENT so
         # that the tables are uploaded, the time-embedding tables rebuilt and (through the (B, T, S) graph cache) nothing re-captured
@@ -616,7 +654,9 @@ class in2INDiffusion(nn.Module):
             self._dirty = False
         return s
 
-    def forward(self, batch):
+    def forward(self, batch, mask=None):
+        """mask: None as the reference's forward hard-codes (in2in.py:326, 338, 350; a "mask" entry of the batch is never read), or the
+        float [B, T, k] key-padding mask for the loop's model_kwargs -- an explicit argument of this port, mode "individual" only."""
         if self.mode == "dual":                      # in2in.py:299-305
             cond = torch.cat([batch["cond_interaction"], batch["cond_interaction_individual1"], batch["cond_interaction_individual2"],
                               batch["cond_individual_individual1"], batch["cond_individual_individual2"]], dim=1)
@@ -633,7 +673,8 @@ class in2INDiffusion(nn.Module):
             s._strategy = self.sampling_strategy
         width = self.nfeats * (1 if self.mode == "individual" else 2)
         x_T = batch["x_T"] if "x_T" in batch else torch.randn(B, T, width, device=s.device)
-        return {"output": s.sample(cond, x_T)}
+        with _KeyMask(s, mask):                      # model_kwargs = {"mask": mask, "cond": cond} of the loop
+            return {"output": s.sample(cond, x_T)}
 
 
 class in2IN(nn.Module):

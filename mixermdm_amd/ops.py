@@ -56,16 +56,27 @@ def adaln(h, ss, ss_rows=None):
     return out
 
 
-def attention(q, k, v, num_heads, kv_seq_shift=0, zero_key=True, causal=False):
+def attention(q, k, v, num_heads, kv_seq_shift=0, zero_key=True, causal=False, key_padding_mask=None):
     """q [nseq, Tq, H*dh], k/v [nseq, Tk, H*dh] (may be column slices of a packed projection); add_zero_attn semantics by default,
-    plain softmax with zero_key=False (optionally causal)."""
+    plain softmax with zero_key=False (optionally causal).
+    key_padding_mask: bool [rows, Tk] in PyTorch's sense (True = ignore the key); key sequence s reads row s % rows (mmdm_attention_masked_f32)."""
     _chk(q, k, v)
+    valid, mask_rows = None, 0
+    if key_padding_mask is not None:
+        if not key_padding_mask.is_cuda or key_padding_mask.dtype != torch.bool or key_padding_mask.dim() != 2 or key_padding_mask.shape[1] != k.shape[1]:
+            raise TypeError("key_padding_mask: a CUDA bool tensor [rows, Tk] is expected (True = ignore)")
+        valid = (~key_padding_mask).to(torch.uint8).contiguous()
+        mask_rows = valid.shape[0]
     nseq, Tq, HD = q.shape
     Tk = k.shape[1]
     for t in (q, k, v):
         assert t.stride(2) == 1 and t.stride(0) == t.shape[1] * t.stride(1), "rows must be uniformly strided"
     out = torch.empty(nseq, Tq, HD, device=q.device, dtype=torch.float32)
     flags = (0 if zero_key else ATTN_NO_ZERO_KEY) | (ATTN_CAUSAL if causal else 0)
+    if valid is not None:
+        check(load_library().mmdm_attention_masked_f32(_p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(out), HD, 0, flags,
+                                                       nseq, Tq, Tk, num_heads, HD // num_heads, kv_seq_shift, C.c_void_p(valid.data_ptr()), mask_rows, _stream()))
+        return out
     check(load_library().mmdm_attention_opts(_p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(out), HD, 0, flags,
                                              nseq, Tq, Tk, num_heads, HD // num_heads, kv_seq_shift, _stream()))
     return out
@@ -129,10 +140,16 @@ def cond_silu(time_tab, step_idx, txt):
     return out
 
 
-def mixer_pre(o1, o2, stats, align=True):
-    _chk(o1, o2, stats)
+def mixer_pre(o1, o2, stats, align=True, last_frame=None):
+    """last_frame: int32 [rows] on the device -- the frame the alignment's displacement of batch row b ends at (row b % rows); None = T - 1."""
+    _chk(o1, o2, stats, last_frame)
     n, T, _ = o1.shape
     out1, out2 = torch.empty_like(o1), torch.empty_like(o2)
+    if last_frame is not None:
+        assert last_frame.dtype == torch.int32 and last_frame.is_contiguous() and last_frame.dim() == 1
+        check(load_library().mmdm_mixer_pre_masked_f32(_p(o1.contiguous()), _p(o2.contiguous()), _p(stats), _p(out1), _p(out2), n, T, int(align),
+                                                       _p(last_frame), last_frame.shape[0], _stream()))
+        return out1, out2
     check(load_library().mmdm_mixer_pre_f32(_p(o1.contiguous()), _p(o2.contiguous()), _p(stats), _p(out1), _p(out2), n, T, int(align), _stream()))
     return out1, out2
 

@@ -162,6 +162,20 @@ class Sampler:
             check(self.lib.mmdm_set_dual_weights(self.h, w.ctypes.data_as(C.c_void_p), len(w)), self.h)
         return w
 
+    # ---- key-padding mask ---------------------------------------------------------------------------
+    def set_key_mask(self, valid):
+        """mmdm_set_key_mask: valid [rows, T] (bool / 0-1; True = the frame exists) or None to clear.  Stays in force for module_forward and
+        begin / run until cleared or replaced; rows = the call's n for module_forward 0, 1, 2, and B for module_forward 4 and the loop."""
+        with torch.cuda.device(self.device):
+            if valid is None:
+                check(self.lib.mmdm_set_key_mask(self.h, None, 0, 0), self.h)
+                return self
+            v = np.ascontiguousarray((torch.as_tensor(valid).detach().cpu().numpy() != 0).astype(np.uint8))
+            if v.ndim != 2:
+                raise ValueError(f"set_key_mask: [rows, T] expected, got {v.shape}")
+            check(self.lib.mmdm_set_key_mask(self.h, v.ctypes.data_as(C.c_void_p), v.shape[0], v.shape[1]), self.h)
+        return self
+
     # ---- sampling ---------------------------------------------------------------------------------
     def begin(self, cond, x_T):
         cond = cond.to(self.device, torch.float32).contiguous()
