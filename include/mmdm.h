@@ -166,6 +166,13 @@ enum { MMDM_ATTN_NO_ZERO_KEY = 1, MMDM_ATTN_CAUSAL = 2 };
 int mmdm_attention_opts(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* O, int ldo, int out_bf16,
                         int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, void* stream);
 
+/* mmdm_attention_ragged_f32 with options: flags = 0 or MMDM_ATTN_NO_ZERO_KEY (plain softmax over each sequence's own keys: the MDM encoder on a
+ * ragged batch, where a sequence is an item's conditioning token + its frames).  Per sequence bit-identical to mmdm_attention_opts with the same
+ * flags on that sequence alone; rows of O outside every sequence are not written.  Every sequence needs >= 1 key.  MMDM_ATTN_CAUSAL on a ragged
+ * launch is MMDM_ERR_UNSUPPORTED (as is a key mask: mmdm_attention_masked_f32). */
+int mmdm_attention_ragged_opts_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int flags,
+                                   int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, int H, int dh, int kv_seq_shift, void* stream);
+
 /* mmdm_attention_opts with a KEY-PADDING mask (nn.MultiheadAttention's key_padding_mask, inverted): key_valid is a DEVICE byte array
  * [mask_rows, Tk], 1 = the key exists, 0 = the key is ignored (logit -inf); key sequence kvseq = (s + kv_seq_shift) % nseq reads row
  * kvseq % mask_rows (mask_rows = 1: one mask for all; mask_rows = the batch size: persons and CFG halves stacked along nseq share their item's
@@ -430,11 +437,15 @@ int mmdm_begin(mmdm_handle h, const float* cond, const float* x_T, int B, int T,
  * processed like any row and never read by a real one); every buffer of k B sequences is k groups.  Where a sequence starts, its length and
  * the (sequence, frame) of every row are DEVICE arrays written on `stream` by this call: GEMMs and row kernels see sum(lens) rows, the
  * attention / PE / AdaLN-conditioning / geometry kernels index through the maps, and a captured step graph depends on (B, rows, query tiles of the
- * longest item, S) only -- it is reused by every ragged batch of the same bucket.  Every item's result is BIT-IDENTICAL to sampling it alone
+ * longest item, S) only -- it is reused by every ragged batch of the same bucket.  With MDMDenoiser as denoiser 1 (model1_kind = 1) the encoder
+ * runs on a second row space, the TOKEN rows (every item's conditioning token in front of its frames: sum(lens) + B rows per group, rounded up
+ * to the same bucket and clipped to max_batch * (max_frames + 1), with maps of their own written by this call), and the graph key grows by the
+ * token stride and the query tiles of the longest TOKEN sequence (64 frames are one tile of frames and two of tokens).  Every item's result is BIT-IDENTICAL to sampling it alone
  * with mmdm_begin (no kernel's arithmetic depends on a row's position in the batch; tests/test_gpu_ragged.py).  mmdm_get_state then points at
  * [rows, 524] buffers whose first sum(lens) rows are the items back to back; history slots (mmdm_set_history) are [2 * rows, C] with the
  * uncond half at row `rows`; mmdm_call_rows returns (rows, sum(lens)).  Covers the two-chain sampler and the single-person sampler over
- * in2IN / InterGen denoisers with head sizes 64 / 128, every precision mode; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
+ * in2IN / InterGen denoisers with head sizes 64 / 128, every precision mode, and over MDMDenoiser as denoiser 1 (head sizes 64 / 128, fp32: the
+ * only precision MDM has); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
  * otherwise MMDM_ERR_UNSUPPORTED / MMDM_ERR_ARG.  mmdm_run / mmdm_seek / mmdm_set_history as after mmdm_begin. */
 int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, void* stream);
 /* Frame rows per half of the CFG-doubled batch in the begun call's buffers (uniform: B * T), the frames that are real (ragged: sum(lens)),

@@ -1174,6 +1174,13 @@ extern "C" int mmdm_attention_ragged_f32(const float* Q, int ldq, const float* K
     return mmdm_attention_opts_rag(Q, ldq, K, ldk, V, ldv, O, ldo, 0, 0, nseq, max_len, max_len, H, dh, kv_seq_shift, &rg, stream);
 }
 
+extern "C" int mmdm_attention_ragged_opts_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int flags,
+                                              int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, int H, int dh, int kv_seq_shift, void* stream) {
+    if (!seq_off || !seq_len || max_len <= 0 || total_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_ragged_opts_f32: bad sequence description");
+    const mmdm_rag_seq rg{seq_off, seq_len, total_rows, max_len};
+    return mmdm_attention_opts_rag(Q, ldq, K, ldk, V, ldv, O, ldo, 0, flags, nseq, max_len, max_len, H, dh, kv_seq_shift, &rg, stream);
+}
+
 // rg != nullptr: ragged batch (kernels.h mmdm_rag_seq); Tq = Tk = the longest sequence
 int mmdm_attention_opts_rag(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* Ov, int ldo, int out_bf16,
                             int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const mmdm_rag_seq* rg, void* stream,
@@ -1202,7 +1209,12 @@ int mmdm_attention_opts_rag(const float* Q, int ldq, const float* K, int ldk, co
         if (mask_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "attention with a key mask: mask_rows=%d must be positive", mask_rows);
     }
     a.key_valid = key_valid; a.mask_rows = key_valid ? mask_rows : 1;
-    if (rg && (flags || !(dh == 128 || dh == 64))) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention on ragged batches: head sizes 64 / 128, zero key, no mask (dh=%d flags=0x%x)", dh, flags);
+    // ragged + MMDM_ATTN_NO_ZERO_KEY (the MDM encoder): the RAG instantiation reads the flag at run time like every other.  Every sequence has >= 1 key, so
+    // the first chunk of every live workgroup holds a visible key and the empty initial state (m = -inf, l = 0) is left with alpha = 0 as in the uniform walk;
+    // a query tile past its sequence's end leaves before it touches the state, a wave without a live query computes no chunk and stores no row (its l = 0 is
+    // never inverted), and the keys of the last partial chunk past Tk score -inf = probability 0 beside at least one finite score.
+    if (rg && ((flags & ~MMDM_ATTN_NO_ZERO_KEY) || !(dh == 128 || dh == 64)))
+        return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention on ragged batches: head sizes 64 / 128, no causal mask, no key mask (dh=%d flags=0x%x)", dh, flags);
     a.shift = ((kv_seq_shift % nseq) + nseq) % nseq;
     a.qtiles = (Tq + QB - 1) / QB;
     a.pairs_per_xcd = (nseq * H + 7) / 8;

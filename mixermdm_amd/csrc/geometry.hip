@@ -546,6 +546,9 @@ int mmdm_blend_cfg_rag(const float* out1, const float* out2, const float* w, int
 // Ragged batches: the row maps of one sampling call, built ON THE DEVICE from the item lengths (passed by value: no host buffer to keep
 // alive, no synchronisation) -- item offsets / lengths, item and frame index of every frame row of a group (-1 / 0 for the padding rows
 // between the sum of lengths and the group stride `rows`), and per sequence of the `groups` x B sequences its first row and length.
+// The MDM denoiser's TOKEN rows (one conditioning token in front of every item's frames) are a second set of maps from the same kernel: lengths + 1,
+// the token stride as `rows`; row_pos 0 is then the token and k >= 1 frame k - 1.  row_seq and item_order may be null (no AdaLN lookup in that stack; the
+// length order of the tokens is the frames').
 // ---------------------------------------------------------------------------------------------------------
 struct RagLens { int v[MMDM_RAG_MAX_ITEMS]; };
 __global__ __launch_bounds__(256) void rag_setup_kernel(RagLens L, int B, int rows, int groups, int* __restrict__ item_off, int* __restrict__ item_len,
@@ -569,7 +572,7 @@ __global__ __launch_bounds__(256) void rag_setup_kernel(RagLens L, int B, int ro
             item = lo; pos = rl - off[lo];
         }
         if (g == 0) { row_item[rl] = item; row_pos[rl] = pos; }
-        row_seq[r] = g * B + (item < 0 ? 0 : item);
+        if (row_seq) row_seq[r] = g * B + (item < 0 ? 0 : item);
     }
     for (int s = tid; s < groups * B; s += nth) { seq_off[s] = (s / B) * rows + off[s % B]; seq_len[s] = L.v[s % B]; }
     for (int b = tid; b < B; b += nth) { item_off[b] = off[b]; item_len[b] = L.v[b]; }

@@ -122,6 +122,10 @@ int mmdm_linear_f32_ex(const float* A, int lda, const float* W, int ldw, int Kw,
 int mmdm_mdm_pack(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
                   int nseq, int T, int D, hipStream_t st);
 int mmdm_mdm_unpack(const float* src, float* dst, int nseq, int T, int D, hipStream_t st);
+// ragged forms (rowops.hip): frame groups `fr` <-> token groups `tk` of `groups` groups, `gpp` groups per person (the CFG halves)
+int mmdm_mdm_pack_rag(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
+                      int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
+int mmdm_mdm_unpack_rag(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
 int mmdm_repack_pose(const float* src, int ld_src, float* dst, int npers, int rows, int ldp, int split, hipStream_t st);
 int mmdm_linear_split_ex(const void* A, int lda, int64_t a_plane, const void* W, int ldw, int64_t w_plane, const float* bias, void* C, int ldc,
                          int64_t c_plane, int out_split, int M, int N, int K, int epilogue, const float* extra, int ld_extra, int period,
@@ -141,6 +145,9 @@ int mmdm_mean_time_rag_nopk(const float* h, float* out, int nseq, const int* seq
 int mmdm_mdm_pack_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
                        int nseq, int T, int D, hipStream_t st);
 int mmdm_mdm_unpack_nopk(const float* src, float* dst, int nseq, int T, int D, hipStream_t st);
+int mmdm_mdm_pack_rag_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
+                           int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
+int mmdm_mdm_unpack_rag_nopk(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
 // silu(time_tab[*step_idx] + txt) as the two fp16 planes of the fp32-split GEMM's A operand (rowops.hip)
 int mmdm_cond_silu_planes(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st);
 int mmdm_cond_silu_planes_nopk(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st);

@@ -186,7 +186,8 @@ struct Scratch {          // transformer-stack work buffers (one set per concurr
 // Row geometry of the current sampling call.  Uniform: B items x T frames, sequence s = rows [s T, (s + 1) T).  Ragged (mmdm_begin_ragged): the B
 // items' frames lie back to back in a GROUP of `rows` rows (sum of the lengths, rounded up to the handle's row bucket); a buffer of k B
 // sequences is k groups; where a sequence starts, how long it is and which sequence / frame a row belongs to are DEVICE arrays, so a captured
-// step graph depends on (B, rows, query tiles of the longest item) only.
+// step graph depends on (B, rows, query tiles of the longest item) only -- and, with MDM as denoiser 1, on the token stride and the query tiles of the
+// longest token sequence.
 struct Geom {
     int B = 0, T = 0;                // items; frames (ragged: the longest item -- sizes the attention grid only)
     bool rag = false;
@@ -195,6 +196,11 @@ struct Geom {
     double tt1 = 0;                  // sum over the items of T_i (T_i + 1): attention FLOP accounting
     const int *seq_off = nullptr, *seq_len = nullptr, *row_seq = nullptr, *item_order = nullptr;
     mmdm_rag rg{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    // ragged call of a handle whose denoiser 1 is MDMDenoiser: the TOKEN rows of its encoder (every item's conditioning token in front of its frames) are a
+    // second row space -- its own group stride (sum of the lengths + B, rounded up to the same bucket), per-sequence (first row, length + 1) and row maps
+    mmdm_rag tk{nullptr, nullptr, nullptr, nullptr, 0, 0};      // tk.rows = 0: no token maps (in2IN denoiser 1)
+    const int *tok_seq_off = nullptr, *tok_seq_len = nullptr;
+    double tok_tt = 0;               // sum over the items of (T_i + 1)^2
     size_t rows_of(int nseq) const { return rag ? (size_t)(nseq / B) * rows : (size_t)nseq * T; }
 };
 
@@ -256,6 +262,8 @@ struct mmdm_handle_s {
     int rag_bucket = 128;                                  // ragged calls: the group stride is the sum of the lengths rounded up to this many rows (MMDM_RAG_BUCKET)
     int *d_rag = nullptr;                                  // ragged row maps: item_off | item_len | row_item | row_pos | row_seq | seq_off | seq_len
     int *d_item_off = nullptr, *d_item_len = nullptr, *d_row_item = nullptr, *d_row_pos = nullptr, *d_row_seq = nullptr, *d_seq_off = nullptr, *d_seq_len = nullptr, *d_item_order = nullptr;
+    int *d_tok = nullptr;                                  // token row maps of an MDM denoiser 1: item_off | item_len | row_item | row_pos | seq_off | seq_len
+    int *d_tok_item_off = nullptr, *d_tok_item_len = nullptr, *d_tok_row_item = nullptr, *d_tok_row_pos = nullptr, *d_tok_seq_off = nullptr, *d_tok_seq_len = nullptr;
 
     // workspace
     Scratch sa, sb;                                        // sa: denoiser1 + Influence, sb: denoiser2 (runs concurrently)
@@ -286,8 +294,9 @@ struct mmdm_handle_s {
     // Captured step graphs, least-recently-used cache keyed by everything a captured node bakes in: (B, T, S).  History
     // destinations, schedule tables, conditioning and the step index are device-side data, not node arguments, so the eval
     // caller's alternating (B, T) requests (src/evaluation/datasets.py:101-122, 438) replay cached graphs instead of re-capturing.
-    // (ragged calls: T = query tiles of the longest item, rows = the group stride; uniform calls: rows = 0)
-    struct GraphEntry { int B, T, S, rows; hipGraphExec_t exec; uint64_t used; hipEvent_t done; int masked; };      // done: recorded behind the entry's last replay
+    // (ragged calls: T = query tiles of the longest item, rows = the group stride; uniform calls: rows = 0.  Ragged calls with MDM as denoiser 1: trows =
+    // the token stride, tT = query tiles of the longest token sequence -- 64 frames are one tile of frames and two of tokens; 0 otherwise)
+    struct GraphEntry { int B, T, S, rows; hipGraphExec_t exec; uint64_t used; hipEvent_t done; int masked; int trows, tT; };      // done: recorded behind the entry's last replay
     std::vector<GraphEntry> graphs;
     size_t graph_cap = 8;
     uint64_t graph_clock = 0;
@@ -545,9 +554,12 @@ int linear(const Ctx& c, const float* A, int lda, const float* W, int ldw, const
 }
 
 // plain self-attention of nn.TransformerEncoderLayer (no zero key)
-int attention_plain(const Ctx& c, const float* qkv, int ld, float* O, int ldo, int nseq, int T, int H, int dh, int flags) {
-    RC(prof_begin(c, 1, 4.0 * nseq * H * (double)T * T * dh, 4.0 * nseq * H * dh * 4.0 * T));
-    RC(mmdm_attention_opts(qkv, ld, qkv + H * dh, ld, qkv + 2 * H * dh, ld, O, ldo, 0, flags, nseq, T, T, H, dh, 0, c.st));
+// rg: the sequences of a ragged launch (the token sequences of a ragged MDM call; T = the longest); `tt` = sum of their squared lengths, `real` = of their lengths
+int attention_plain(const Ctx& c, const float* qkv, int ld, float* O, int ldo, int nseq, int T, int H, int dh, int flags, const mmdm_rag_seq* rg = nullptr,
+                    double tt = 0, double real = 0) {
+    if (rg) RC(prof_begin(c, 1, 4.0 * (nseq / rg->items) * H * dh * tt, 4.0 * (nseq / rg->items) * H * dh * 4.0 * real));
+    else RC(prof_begin(c, 1, 4.0 * nseq * H * (double)T * T * dh, 4.0 * nseq * H * dh * 4.0 * T));
+    RC(mmdm_attention_opts_rag(qkv, ld, qkv + H * dh, ld, qkv + 2 * H * dh, ld, O, ldo, 0, flags, nseq, T, T, H, dh, 0, rg, c.st));
     return prof_end(c, 1);
 }
 
@@ -781,11 +793,14 @@ int run_denoiser(const Ctx& c, const ModuleW& m, bool interaction, const float* 
 // One nn.TransformerEncoderLayer on x [nseq*T, D] in place.  norm_first = 0 (torch default, MDM / clipTransEncoder):
 //   x = LN1(x + SA(x)); x = LN2(x + W2 act(W1 x)).   norm_first = 1 (CLIP ResidualAttentionBlock): x += SA(LN1 x); x += W2 act(W1 LN2 x).
 // ws: qkv [R,3D] | att [R,D] | tmp [R,D] | f1 [R,F].
+// rg (a ragged MDM call): the nseq sequences are rg's, in groups of rg->total_rows rows in all (padding rows included) -- the GEMMs and LayerNorm run on
+// every row, the attention walks the sequences; T = the longest.
 int encoder_layer(const Ctx& c, float* x, const EncLayerW& w, int nseq, int T, int D, int H, int F, bool norm_first, int act_epi, bool causal,
-                  float eps, float* qkv, float* att, float* tmp, float* f1) {
-    const int R = nseq * T, dh = D / H;
+                  float eps, float* qkv, float* att, float* tmp, float* f1, const mmdm_rag_seq* rg = nullptr, double rg_tt = 0, double rg_real = 0) {
+    const int R = rg ? rg->total_rows : nseq * T, dh = D / H;
     const int flags = MMDM_ATTN_NO_ZERO_KEY | (causal ? MMDM_ATTN_CAUSAL : 0);
     if (norm_first) {
+        if (rg) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "encoder layer: ragged batches cover the post-norm form only");
         RC(ROWOP(c, mmdm_layernorm_f32, x, w.n1_g, w.n1_b, tmp, R, D, eps, c.st));
         RC(linear(c, tmp, D, w.in_w, D, w.in_b, qkv, 3 * D, R, 3 * D, D));
         RC(attention_plain(c, qkv, 3 * D, att, D, nseq, T, H, dh, flags));
@@ -795,7 +810,7 @@ int encoder_layer(const Ctx& c, float* x, const EncLayerW& w, int nseq, int T, i
         return linear(c, f1, F, w.l2_w, F, w.l2_b, x, D, R, D, F, MMDM_EPI_BIAS_RESID, x, D);
     }
     RC(linear(c, x, D, w.in_w, D, w.in_b, qkv, 3 * D, R, 3 * D, D));
-    RC(attention_plain(c, qkv, 3 * D, att, D, nseq, T, H, dh, flags));
+    RC(attention_plain(c, qkv, 3 * D, att, D, nseq, T, H, dh, flags, rg, rg_tt, rg_real));
     RC(linear(c, att, D, w.out_w, D, w.out_b, tmp, D, R, D, D, MMDM_EPI_BIAS_RESID, x, D));
     RC(ROWOP(c, mmdm_layernorm_f32, tmp, w.n1_g, w.n1_b, x, R, D, eps, c.st));
     RC(linear(c, x, D, w.l1_w, D, w.l1_b, f1, F, R, F, D, act_epi));
@@ -810,18 +825,31 @@ int run_denoiser_mdm(const Ctx& c, const ModuleW& m, const float* x, int xb, int
     const Scratch& S = *c.s;
     const int D = m.st.D, nseq = npers * n;
     // pose embeddings + pe[1 + t] (token 0 is the conditioning token) into S.att, then assemble [nseq, T+1, D] in S.h
-    RC(repack(c, m, x, ldx, S.xp, npers, xb * T));
+    // (ragged: frame groups in S.att -- m.pe_r holds pe[1 + frame] of every frame row -- and token groups in S.h, through the two sets of maps)
+    RC(repack(c, m, x, ldx, S.xp, npers, (int)c.rows_of(xb, T)));
     for (int p = 0; p < npers; ++p)
         for (int rep = 0; rep < n / xb; ++rep)
-            RC(embed(c, m, S.xp, p, S.att + ((size_t)p * n + (size_t)rep * xb) * T * D, xb, T, 1));
+            RC(embed(c, m, S.xp, p, S.att + c.rows_of(p * n + rep * xb, T) * D, xb, T, 1));
+    if (c.rag()) {
+        const Geom& g = *c.g;
+        if (!g.tk.rows) return mmdm_set_error(MMDM_ERR_STATE, "ragged MDM denoiser: the call has no token maps");
+        const int groups = nseq / g.B;
+        const mmdm_rag_seq tseq{g.tok_seq_off, g.tok_seq_len, groups * g.tk.rows, T + 1, g.item_order, g.B};
+        RC(ROWOP(c, mmdm_mdm_pack_rag, S.att, cond, ldc, m.time_tab, c.h->d_step, m.pe, S.h, groups, n / g.B, D, g.rg, g.tk, c.st));
+        for (int l = 0; l < m.st.L; ++l)
+            RC(encoder_layer(c, S.h, m.enc[l], nseq, T + 1, D, m.st.H, m.st.F, false, MMDM_EPI_BIAS_GELU, false, 1e-5f, S.qkv, S.att, S.xn, S.f1, &tseq, g.tok_tt,
+                             (double)g.real_rows + g.B));
+        RC(ROWOP(c, mmdm_mdm_unpack_rag, S.h, S.att, groups, D, g.rg, g.tk, c.st));
+    } else {
+        for (int p = 0; p < npers; ++p)
+            RC(ROWOP(c, mmdm_mdm_pack, S.att + (size_t)p * n * T * D, cond + (size_t)p * D, ldc, m.time_tab, c.h->d_step, m.pe,
+                             S.h + (size_t)p * n * (T + 1) * D, n, T, D, c.st));
+        for (int l = 0; l < m.st.L; ++l)
+            RC(encoder_layer(c, S.h, m.enc[l], nseq, T + 1, D, m.st.H, m.st.F, false, MMDM_EPI_BIAS_GELU, false, 1e-5f, S.qkv, S.att, S.xn, S.f1));
+        RC(ROWOP(c, mmdm_mdm_unpack, S.h, S.att, nseq, T, D, c.st));
+    }
     for (int p = 0; p < npers; ++p)
-        RC(ROWOP(c, mmdm_mdm_pack, S.att + (size_t)p * n * T * D, cond + (size_t)p * D, ldc, m.time_tab, c.h->d_step, m.pe,
-                         S.h + (size_t)p * n * (T + 1) * D, n, T, D, c.st));
-    for (int l = 0; l < m.st.L; ++l)
-        RC(encoder_layer(c, S.h, m.enc[l], nseq, T + 1, D, m.st.H, m.st.F, false, MMDM_EPI_BIAS_GELU, false, 1e-5f, S.qkv, S.att, S.xn, S.f1));
-    RC(ROWOP(c, mmdm_mdm_unpack, S.h, S.att, nseq, T, D, c.st));
-    for (int p = 0; p < npers; ++p)
-        RC(linear(c, S.att + (size_t)p * n * T * D, D, m.out_w, D, m.out_b, out + (size_t)p * NF, ldo, n * T, NF, D));
+        RC(linear(c, S.att + c.rows_of(p * n, T) * D, D, m.out_w, D, m.out_b, out + (size_t)p * NF, ldo, (int)c.rows_of(n, T), NF, D));
     return MMDM_OK;
 }
 
@@ -1216,7 +1244,7 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     }
     if (const char* e = getenv("MMDM_GRAPH_CACHE")) { long v = atol(e); if (v >= 1 && v <= 64) h->graph_cap = (size_t)v; }
     // ragged calls (mmdm_begin_ragged): row maps for up to 4 groups of max_batch * max_frames rows, and per module the PE rows of a group
-    if (so <= 1 && !mdm) {
+    if (so <= 1) {
         const size_t cap = (size_t)B * T, nb = (size_t)(B < MMDM_RAG_MAX_ITEMS ? B : MMDM_RAG_MAX_ITEMS), G = 4;
         if ((rc = dalloc(h, &tmp, 3 * nb + 2 * cap + G * cap + 2 * G * nb))) return fail(rc);
         h->d_rag = reinterpret_cast<int*>(tmp);
@@ -1225,6 +1253,13 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
         if (has_d1 && (rc = dalloc(h, &h->d1.pe_r, cap * D1))) return fail(rc);
         if (has_d2 && (rc = dalloc(h, &h->d2.pe_r, cap * D))) return fail(rc);
         if (has_mx && (rc = dalloc(h, &h->mx.pe_r, cap * Dm))) return fail(rc);
+        if (mdm) {      // token rows of the MDM encoder: up to max_batch * (max_frames + 1) per group
+            const size_t tcap = (size_t)B * (T + 1);
+            if ((rc = dalloc(h, &tmp, 2 * nb + 2 * tcap + 2 * G * nb))) return fail(rc);
+            h->d_tok = reinterpret_cast<int*>(tmp);
+            h->d_tok_item_off = h->d_tok; h->d_tok_item_len = h->d_tok_item_off + nb; h->d_tok_row_item = h->d_tok_item_len + nb;
+            h->d_tok_row_pos = h->d_tok_row_item + tcap; h->d_tok_seq_off = h->d_tok_row_pos + tcap; h->d_tok_seq_len = h->d_tok_seq_off + G * nb;
+        }
         if (const char* e = getenv("MMDM_RAG_BUCKET")) { long v = atol(e); if (v >= 1 && v <= 4096) h->rag_bucket = (int)v; }
     }
     *out = h;
@@ -1446,8 +1481,8 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     if (lens && h->mask_rows)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: a key mask is set on the handle; ragged batches carry their lengths instead (clear it with mmdm_set_key_mask(h, NULL, 0, 0))"));
     if (lens) {
-        if (h->cfg.single_only > 1 || h->d1.kind == 1 || !h->d_rag)
-            return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: ragged batches cover the two-chain MixerMDM sampler and the single-person sampler over in2IN / InterGen denoisers"));
+        if (h->cfg.single_only > 1 || !h->d_rag || (h->d1.kind == 1 && !h->d_tok))
+            return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: ragged batches cover the two-chain MixerMDM sampler and the single-person sampler over in2IN / InterGen / MDM denoisers"));
         const StackW* sts[3] = {h->cfg.single_only != 2 ? &h->d1.st : nullptr, h->cfg.single_only != 1 ? &h->d2.st : nullptr, h->cfg.single_only == 0 ? &h->mx.st : nullptr};
         for (const StackW* w : sts)
             if (w && w->D / w->H != 64 && w->D / w->H != 128)
@@ -1468,6 +1503,14 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
         g.rag = true; g.rows = (int)rows; g.real_rows = (int)sum; g.tt1 = tt1;
         g.seq_off = h->d_seq_off; g.seq_len = h->d_seq_len; g.row_seq = h->d_row_seq; g.item_order = h->d_item_order;
         g.rg = mmdm_rag{h->d_row_item, h->d_row_pos, h->d_item_off, h->d_item_len, B, (int)rows};
+        if (h->d1.kind == 1) {      // MDM: the token group holds sum + B rows; its stride is rounded and clipped like the frame stride, independently of it
+            const long tcap = (long)h->cfg.max_batch * (h->cfg.max_frames + 1);
+            long trows = (sum + B + h->rag_bucket - 1) / h->rag_bucket * h->rag_bucket;
+            if (trows > tcap) trows = tcap;
+            g.tk = mmdm_rag{h->d_tok_row_item, h->d_tok_row_pos, h->d_tok_item_off, h->d_tok_item_len, B, (int)trows};
+            g.tok_seq_off = h->d_tok_seq_off; g.tok_seq_len = h->d_tok_seq_len;
+            for (int b = 0; b < B; ++b) g.tok_tt += (double)(lens[b] + 1) * (lens[b] + 1);
+        }
     } else {
         if (B <= 0 || B > h->cfg.max_batch || T <= 0 || T > h->cfg.max_frames)
             return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_begin: B=%d T=%d exceed the handle's max_batch=%d / max_frames=%d", B, T, h->cfg.max_batch, h->cfg.max_frames));
@@ -1489,8 +1532,15 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     };
     if (g.rag) {
         RC(herr(h, mmdm_rag_setup(lens, B, g.rows, 4, h->d_item_off, h->d_item_len, h->d_row_item, h->d_row_pos, h->d_row_seq, h->d_seq_off, h->d_seq_len, h->d_item_order, st)));
+        // (MDMDenoiser: frame t takes pe[1 + t] -- row 0 belongs to the conditioning token)
         for (ModuleW* m : {&h->d1, &h->d2, &h->mx})
-            if (m->pe_r && m->pe) RC(herr(h, mmdm_gather_rows(m->pe, h->d_row_pos, m->pe_r, g.rows, m->st.D, st)));
+            if (m->pe_r && m->pe) RC(herr(h, mmdm_gather_rows(m->pe + (m->kind == 1 ? m->st.D : 0), h->d_row_pos, m->pe_r, g.rows, m->st.D, st)));
+        if (g.tk.rows) {
+            int tl[MMDM_RAG_MAX_ITEMS];
+            for (int b = 0; b < B; ++b) tl[b] = lens[b] + 1;
+            RC(herr(h, mmdm_rag_setup(tl, B, g.tk.rows, 4, h->d_tok_item_off, h->d_tok_item_len, h->d_tok_row_item, h->d_tok_row_pos, nullptr, h->d_tok_seq_off,
+                                      h->d_tok_seq_len, nullptr, st)));
+        }
     }
     if (h->cfg.single_only == 3 && !h->dual_w_set) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_begin: call mmdm_set_dual_weights after mmdm_set_schedule"));
     ProfPause pause(h->prof);
@@ -1596,9 +1646,11 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
         hipEvent_t done = nullptr;
         int first = 0;
         // what a captured node bakes in: uniform (B, T, S); ragged (B, query tiles of the longest item, S, group stride) -- the lengths are device data
+        // (+ with MDM as denoiser 1: the token stride and the query tiles of the longest token sequence, T + 1 rows)
         const int kT = h->geom.rag ? (h->T + 63) / 64 : h->T, kR = h->geom.rag ? h->geom.rows : 0;
+        const int kTR = h->geom.rag ? h->geom.tk.rows : 0, kTT = kTR ? (h->T + 1 + 63) / 64 : 0;
         for (auto& g : h->graphs)
-            if (g.B == h->B && g.T == kT && g.S == h->S && g.rows == kR && g.masked == masked) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
+            if (g.B == h->B && g.T == kT && g.S == h->S && g.rows == kR && g.masked == masked && g.trows == kTR && g.tT == kTT) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
         if (!exec) {
             hipGraph_t g = nullptr;
             // one capture at a time in the process: several handles may be driven from several host threads (mmdm_create_shared), and two
@@ -1632,7 +1684,7 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
                 (void)hipGraphExecDestroy(exec);
                 return herr(h, mmdm_set_error(MMDM_ERR_HIP, "mmdm_run: hipEventCreate: %s", hipGetErrorString(e)));
             }
-            h->graphs.push_back({h->B, kT, h->S, kR, exec, ++h->graph_clock, done, masked});
+            h->graphs.push_back({h->B, kT, h->S, kR, exec, ++h->graph_clock, done, masked, kTR, kTT});
             ++h->n_captures;
             // the FIRST launch of a fresh exec binds the runtime's internal branch streams to it (hip::Graph::UpdateStreams): still inside the
             // exclusive section -- beside another thread's launch that is where the runtime was seen to crash

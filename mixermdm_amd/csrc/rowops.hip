@@ -217,6 +217,40 @@ __global__ void mdm_unpack_kernel(const float* __restrict__ src, float* __restri
     dst[i] = src[(row + row / T + 1) * D + d];
 }
 
+// The two passes on a RAGGED batch (kernels.h mmdm_rag): the frame rows of a group (`fr`: items back to back, stride fr.rows) and its token rows
+// (`tk`: every item's conditioning token in front of its frames, stride tk.rows; tk.row_pos 0 = the token, k >= 1 = frame k - 1) are two row spaces.
+//   dst[g, r, :] = 0                                                             padding token row (tk.row_item[r] < 0)
+//                = (cond[(g % gpp) B + item, p D + :] + time_tab[*step, :]) + pe[0, :]     the token of `item`; p = g / gpp = the person of group g
+//                = src[g, fr.item_off[item] + pos - 1, :]                        frame pos - 1 of `item`
+// (same association order of the token's sum as mdm_pack_kernel: the bits of the uniform path)
+__global__ void mdm_pack_rag_kernel(const float* __restrict__ src, const float* __restrict__ cond, int ldc, const float* __restrict__ time_tab,
+                                    const int* __restrict__ step_idx, const float* __restrict__ pe, float* __restrict__ dst, int groups, int gpp, int D,
+                                    mmdm_rag fr, mmdm_rag tk) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)groups * tk.rows * D) return;
+    const int d = (int)(i % D);
+    const size_t row = i / D;
+    const int r = (int)(row % tk.rows), g = (int)(row / tk.rows);
+    const int item = tk.row_item[r], pos = tk.row_pos[r];
+    float y = 0.f;
+    if (item >= 0) {
+        if (pos == 0) y = (cond[((size_t)(g % gpp) * tk.B + item) * ldc + (size_t)(g / gpp) * D + d] + time_tab[(size_t)(*step_idx) * D + d]) + pe[d];
+        else y = src[((size_t)g * fr.rows + fr.item_off[item] + (pos - 1)) * D + d];
+    }
+    dst[i] = y;
+}
+
+// dst[g, r, :] = src[g, tk.item_off[item] + 1 + pos, :] for frame row r = (item, pos) of a group; padding frame rows are written as zeros
+__global__ void mdm_unpack_rag_kernel(const float* __restrict__ src, float* __restrict__ dst, int groups, int D, mmdm_rag fr, mmdm_rag tk) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)groups * fr.rows * D) return;
+    const int d = (int)(i % D);
+    const size_t row = i / D;
+    const int r = (int)(row % fr.rows), g = (int)(row / fr.rows);
+    const int item = fr.row_item[r];
+    dst[i] = item < 0 ? 0.f : src[((size_t)g * tk.rows + tk.item_off[item] + 1 + fr.row_pos[r]) * D + d];
+}
+
 // out[b, l, :] = table[tokens[b, l], :] + pos[l, :]   (CLIP token + positional embedding: src/models/mixermdm.py:298-299)
 __global__ void token_embed_kernel(const float* __restrict__ table, const int* __restrict__ tokens, const float* __restrict__ pos,
                                    float* __restrict__ out, int n, int L, int D, int vocab) {
@@ -398,6 +432,21 @@ int RO(mmdm_mdm_unpack)(const float* src, float* dst, int nseq, int T, int D, hi
     if (n == 0) return MMDM_OK;
     hipLaunchKernelGGL(mdm_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, nseq, T, D);
     return mmdm_check_launch("mdm_unpack");
+}
+
+int RO(mmdm_mdm_pack_rag)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
+                          int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st) {
+    const size_t n = (size_t)groups * tk.rows * D;
+    if (n == 0) return MMDM_OK;
+    hipLaunchKernelGGL(mdm_pack_rag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, fr, tk);
+    return mmdm_check_launch("mdm_pack_rag");
+}
+
+int RO(mmdm_mdm_unpack_rag)(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st) {
+    const size_t n = (size_t)groups * fr.rows * D;
+    if (n == 0) return MMDM_OK;
+    hipLaunchKernelGGL(mdm_unpack_rag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, groups, D, fr, tk);
+    return mmdm_check_launch("mdm_unpack_rag");
 }
 
 #ifndef MMDM_ROWOPS_NOPK

@@ -82,6 +82,24 @@ def attention(q, k, v, num_heads, kv_seq_shift=0, zero_key=True, causal=False, k
     return out
 
 
+def attention_ragged(q, k, v, num_heads, seq_off, seq_len, max_len, kv_seq_shift=0, zero_key=True, causal=False, out=None):
+    """Attention over a ragged batch (mmdm_attention_ragged_opts_f32): q / k / v [rows, H*dh] (may be column slices of a packed projection), sequence
+    s = rows [seq_off[s], seq_off[s] + seq_len[s]) with seq_off / seq_len int32 device tensors; max_len >= every length.  Rows outside every
+    sequence are left as they are in `out` (a new tensor: uninitialised)."""
+    _chk(q, k, v, seq_off, seq_len)
+    assert seq_off.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_off.numel() == seq_len.numel()
+    rows, HD = q.shape
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.stride(1) == 1
+    if out is None:
+        out = torch.empty(rows, HD, device=q.device, dtype=torch.float32)
+    flags = (0 if zero_key else ATTN_NO_ZERO_KEY) | (ATTN_CAUSAL if causal else 0)
+    check(load_library().mmdm_attention_ragged_opts_f32(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(out), out.stride(0), flags,
+                                                        seq_off.numel(), _p(seq_off), _p(seq_len), int(max_len), rows, num_heads, HD // num_heads, kv_seq_shift,
+                                                        _stream()))
+    return out
+
+
 def layernorm(x, weight, bias, eps=1e-5):
     """nn.LayerNorm over the last dimension with affine parameters."""
     _chk(x, weight, bias)
