@@ -154,7 +154,7 @@ int mmdm_attention_ex(const float* Q, int ldq, const float* K, int ldk, const fl
 /* mmdm_attention_f32 over a RAGGED batch: sequence s owns rows [seq_off[s], seq_off[s] + seq_len[s]) of Q / K / V / O (DEVICE int arrays of nseq
  * entries; the K/V sequence of s is (s + kv_seq_shift) % nseq and may have another length); max_len >= every length sizes the grid; total_rows =
  * rows of O.  dh = 64 or 128.  Per sequence bit-identical to mmdm_attention_f32 on that sequence alone.  (The 16-bit forms have the same ragged
- * instantiations inside the sampler: mmdm_begin_ragged.) */
+ * instantiations inside the sampler: mmdm_begin_ragged; the two-plane form also as mmdm_attention_split_ragged.) */
 int mmdm_attention_ragged_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                               int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, int H, int dh, int kv_seq_shift, void* stream);
 
@@ -208,6 +208,14 @@ int mmdm_attention_bf16(const void* Qp, int ldq, const void* Kp, int ldk, const 
  * As accurate against float64 as mmdm_attention_f32 (tests), ~2.5x faster.  out_mode / flags as mmdm_attention_planes.  dh = 64 or 128. */
 int mmdm_attention_split(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, const void* Vp, int ldv, int64_t v_plane,
                          void* O, int ldo, int out_mode, int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, void* stream);
+
+/* mmdm_attention_split over a RAGGED batch (sequence description as mmdm_attention_ragged_f32; O rows / planes of total_rows rows).  flags = 0 or
+ * MMDM_ATTN_NO_ZERO_KEY (the MDM encoder of a precision-2 handle on a ragged batch: plain softmax over each token sequence's own keys; every sequence
+ * needs >= 1 key).  Per sequence bit-identical to mmdm_attention_split with the same flags on that sequence alone; rows of O outside every sequence are
+ * not written.  MMDM_ATTN_CAUSAL on a ragged launch is MMDM_ERR_UNSUPPORTED. */
+int mmdm_attention_split_ragged(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, const void* Vp, int ldv, int64_t v_plane,
+                                void* O, int ldo, int out_mode, int flags, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows,
+                                int H, int dh, int kv_seq_shift, void* stream);
 
 /* out[r,:] = silu(time_row[:] + txt[r,:]) for r < rows; time_row = time_tab + (*step_idx) * D.
  * Replaces `embed_timestep(t) + text_embed(c)` followed by AdaLN's SiLU  in2in.py:415-422, layers.py:9-10. */
@@ -282,6 +290,16 @@ int mmdm_dual_ddim_f32(const float* m_ind, const float* m_int, const float* coef
  * Replaces norm1/norm2 of nn.TransformerEncoderLayer (src/models/mdm.py:252-264), clip_ln (src/models/mixermdm.py:259), ln_final. */
 int mmdm_layernorm_f32(const float* x, const float* gamma, const float* beta, float* out, int rows, int D, float eps, void* stream);
 
+/* mmdm_layernorm_f32 that ALSO writes the result as the two fp16 planes of the fp32-split mode (planes [2][rows][D] fp16, plane_stride in elements,
+ * >= rows * D and a multiple of 8; h = fp16(y), l = fp16((y - h) * 2048)) in the same pass: the row is read once and stays in registers.  A post-norm
+ * encoder layer uses its normalised row as the next residual (fp32) and as the next GEMM's operand (planes); this is LN1 / LN2 of MDMDenoiser's encoder
+ * in a precision-2 handle.  `out` is bitwise mmdm_layernorm_f32's, the planes are bitwise mmdm_f32_split of it.  |y| < 65504.
+ * build: the library holds its row kernels twice (mmdm_create_shared has the story): 0 = the build behind mmdm_layernorm_f32, 1 = the build without
+ * packed-fp32 instructions that every precision 1-3 handle runs (reductions by DPP / v_permlane*_swap: the last bits of mean and variance may differ
+ * from build 0).  planes == NULL: the plain LayerNorm of that build (plane_stride ignored). */
+int mmdm_layernorm_split(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
+                         int build, void* stream);
+
 /* out[b,l,:] = table[tokens[b,l],:] + pos[l,:]; tokens: DEVICE int32 [n,L], clamped to [0, vocab).
  * Replaces token_embedding(text) + positional_embedding  src/models/mixermdm.py:298-299. */
 int mmdm_token_embed_f32(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, void* stream);
@@ -354,7 +372,10 @@ typedef struct {
                         *    the embedding / the conditioning projections of precision 1 / 3 handles on the fp32 MFMA kernel (no range limit there). */
     int model1_kind;   /* 0 = in2IN individual denoiser, 1 = MDMDenoiser (post-norm nn.TransformerEncoder with a conditioning token,
                         *    src/models/mdm.py:234-298; MODEL1.NAME == "MDM", src/models/mixermdm.py:32-40, 264-265).  Its cond slices are
-                        *    latent-sized (mdm.py:279), so the mixer's cond rows are [3*text_dim | 2*d1_latent | 3*text_dim] */
+                        *    latent-sized (mdm.py:279), so the mixer's cond rows are [3*text_dim | 2*d1_latent | 3*text_dim].
+                        *    Precision: 0 (fp32) and 2 (fp32-split: the encoder's four GEMMs per layer on fp16-plane twins of its weights, the
+                        *    two-plane attention, LayerNorm / sequence assembly writing fp32 rows + planes in one pass -- needs head size 64 or
+                        *    128, MDM's own 256 / 4 heads gives 64); precision 1 and 3 with model1_kind = 1 are MMDM_ERR_UNSUPPORTED */
     int d1_latent, d1_ff, d1_layers, d1_heads;   /* denoiser1's own sizes (MODEL1 is a separate config); 0 = same as d_* */
 } mmdm_config;
 
@@ -444,8 +465,8 @@ int mmdm_begin(mmdm_handle h, const float* cond, const float* x_T, int B, int T,
  * with mmdm_begin (no kernel's arithmetic depends on a row's position in the batch; tests/test_gpu_ragged.py).  mmdm_get_state then points at
  * [rows, 524] buffers whose first sum(lens) rows are the items back to back; history slots (mmdm_set_history) are [2 * rows, C] with the
  * uncond half at row `rows`; mmdm_call_rows returns (rows, sum(lens)).  Covers the two-chain sampler and the single-person sampler over
- * in2IN / InterGen denoisers with head sizes 64 / 128, every precision mode, and over MDMDenoiser as denoiser 1 (head sizes 64 / 128, fp32: the
- * only precision MDM has); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
+ * in2IN / InterGen denoisers with head sizes 64 / 128, every precision mode, and over MDMDenoiser as denoiser 1 (head sizes 64 / 128, fp32 and
+ * fp32-split: the precisions MDM has); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
  * otherwise MMDM_ERR_UNSUPPORTED / MMDM_ERR_ARG.  mmdm_run / mmdm_seek / mmdm_set_history as after mmdm_begin. */
 int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, void* stream);
 /* Frame rows per half of the CFG-doubled batch in the begun call's buffers (uniform: B * T), the frames that are real (ragged: sum(lens)),

@@ -100,6 +100,8 @@ SYMBOLS = {
     "mmdm_call_rows": (_I, [_VP, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "mmdm_attention_ragged_f32": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "mmdm_attention_ragged_opts_f32": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
+    "mmdm_attention_split_ragged": (_I, [_VP, _I, C.c_int64, _VP, _I, C.c_int64, _VP, _I, C.c_int64, _VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
+    "mmdm_layernorm_split": (_I, [_VP, _VP, _VP, _VP, _VP, C.c_int64, _I, _I, C.c_float, _I, _VP]),
     "mmdm_set_history": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I]),
     "mmdm_run": (_I, [_VP, _I, _I, _VP]),
     "mmdm_seek": (_I, [_VP, _I, _VP]),

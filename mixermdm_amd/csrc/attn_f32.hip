@@ -1260,6 +1260,16 @@ extern "C" int mmdm_attention_split(const void* Qp, int ldq, int64_t q_plane, co
     return mmdm_attention_planes_ex(Qp, ldq, q_plane, Kp, ldk, k_plane, 2, nullptr, 0, Vp, ldv, v_plane, O, ldo, out_mode, flags, nseq, Tq, Tk, H, dh, kv_seq_shift, stream);
 }
 
+// mmdm_attention_split over a ragged batch (sequence description as mmdm_attention_ragged_f32)
+extern "C" int mmdm_attention_split_ragged(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, const void* Vp, int ldv, int64_t v_plane,
+                                           void* O, int ldo, int out_mode, int flags, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows,
+                                           int H, int dh, int kv_seq_shift, void* stream) {
+    if (!Vp) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_split_ragged: V is null");
+    if (!seq_off || !seq_len || max_len <= 0 || total_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_split_ragged: bad sequence description");
+    const mmdm_rag_seq rg{seq_off, seq_len, total_rows, max_len};
+    return mmdm_attention_planes_ex(Qp, ldq, q_plane, Kp, ldk, k_plane, 2, nullptr, 0, Vp, ldv, v_plane, O, ldo, out_mode, flags, nseq, max_len, max_len, H, dh, kv_seq_shift, stream, &rg);
+}
+
 // Vp != nullptr, one plane: V also as bf16 rows [rows][ldvp] -> P.V on the bf16 matrix cores (attn_qkp_kernel<DH, 1, true>);
 // nplanes == 2: Q, K and V (Vp, plane stride v_plane) as the two fp16 planes of the fp32-split mode (attn_qkp_kernel<DH, 2, true, true>)
 int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, int nplanes, const float* V, int ldv,
@@ -1290,7 +1300,20 @@ int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const voi
     a.seq_off = rg ? rg->off : nullptr; a.seq_len = rg ? rg->len : nullptr;
     a.seq_order = (rg && rg->order && rg->items > 0 && nseq % rg->items == 0) ? rg->order : nullptr; a.order_items = rg ? rg->items : 0;
     a.o_plane = (size_t)(rg ? (size_t)rg->total_rows : (size_t)nseq * Tq) * ldo;
-    if (rg && flags) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention on ragged batches: zero key, no mask (flags=0x%x)", flags);
+    // ragged + MMDM_ATTN_NO_ZERO_KEY, two-plane form only (the MDM encoder of a precision-2 handle): attn_qkp_kernel's RAG instantiation reads the flag at run
+    // time like the uniform one, and was read for the three places where the empty initial state (m = -inf, l = 0) could meet the ragged walk:
+    //   - a query tile past its sequence's end (qt * QB >= G.Tq) returns before the first barrier and before m / l exist: the whole workgroup leaves;
+    //   - a wave with no live query (q0 >= G.Tq) in a live workgroup keeps staging and the barriers and skips every chunk's arithmetic, so its state stays
+    //     (-inf, 0) -- and its l = 0 is never inverted: the store loop drops every row with qrow >= G.Tq before it forms 1 / l (a lane past Tq inside a live
+    //     wave computes a copy of the last query, finite, and is dropped the same way);
+    //   - every chunk the loop visits starts at c0 < Tk (nchunks = ceil(Tk / 16), Tk >= 1), so it holds at least one key <= kmax with a finite score: the keys
+    //     of the last partial chunk past Tk (zero rows: they lie outside the sequence's buffer resource) score -inf = probability 0, cmax is finite, the first
+    //     chunk leaves the empty state with m_new = cmax and alpha = exp2(-inf) = 0 on o = 0, l = 0, and exp2(-inf - (-inf)) is never formed.
+    // The kernel is therefore launched as it stands.  Causal launches stay refused (the causal chunk bound is per query tile), as does the flag on the
+    // one-plane form, which nothing needs.
+    if (rg && flags && (nplanes != 2 || (flags & ~MMDM_ATTN_NO_ZERO_KEY)))
+        return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention on ragged batches: no causal mask, no key mask; MMDM_ATTN_NO_ZERO_KEY on the two-plane form only (planes=%d flags=0x%x)",
+                              nplanes, flags);
     a.shift = ((kv_seq_shift % nseq) + nseq) % nseq;
     a.qtiles = (Tq + QB - 1) / QB;
     a.pairs_per_xcd = (nseq * H + 7) / 8;

@@ -148,6 +148,18 @@ int mmdm_mdm_unpack_nopk(const float* src, float* dst, int nseq, int T, int D, h
 int mmdm_mdm_pack_rag_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
                            int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
 int mmdm_mdm_unpack_rag_nopk(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
+// Row kernels of the fp32-split post-norm encoder (MDMDenoiser, precision 2; rowops.hip, both builds): LayerNorm and the sequence assembly write the fp32
+// rows (residual) and their two fp16 planes (GEMM operand: planes [2][rows][D], plane stride in elements) in one pass
+int mmdm_layernorm_planes(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps, hipStream_t st);
+int mmdm_layernorm_planes_nopk(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps, hipStream_t st);
+int mmdm_mdm_pack_planes(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                         int64_t plane_stride, int nseq, int T, int D, hipStream_t st);
+int mmdm_mdm_pack_planes_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                              int64_t plane_stride, int nseq, int T, int D, hipStream_t st);
+int mmdm_mdm_pack_rag_planes(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                             int64_t plane_stride, int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
+int mmdm_mdm_pack_rag_planes_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                                  int64_t plane_stride, int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
 // silu(time_tab[*step_idx] + txt) as the two fp16 planes of the fp32-split GEMM's A operand (rowops.hip)
 int mmdm_cond_silu_planes(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st);
 int mmdm_cond_silu_planes_nopk(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st);

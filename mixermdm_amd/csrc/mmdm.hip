@@ -160,6 +160,8 @@ struct StackW {          // a transformer stack: denoiser blocks or Influence bl
 
 struct EncLayerW {       // one nn.TransformerEncoderLayer (post-norm): MDMDenoiser.seqTransEncoder.layers.{i}  src/models/mdm.py:252-264
     float *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_g, *n1_b, *n2_g, *n2_b;
+    // precision 2 (MDMDenoiser): the four GEMM weights as two fp16 planes, made at mmdm_prepare like a stack's twins (fragment order when ModuleW::st.w_packed)
+    void *in_s = nullptr, *out_s = nullptr, *l1_s = nullptr, *l2_s = nullptr;
 };
 
 struct ModuleW {         // denoiser or mixer front/back ends
@@ -476,9 +478,21 @@ int build_module_mdm(mmdm_handle h, ModuleW& m, const std::string& pfx, int D, i
     RC(add_slot(h, pfx + "embed_timestep.time_embed.2.bias", &m.t2_b, D, 1));
     RC(add_slot(h, pfx + "output_process.poseFinal.weight", &m.out_w, NF, D));
     RC(add_slot(h, pfx + "output_process.poseFinal.bias", &m.out_b, NF, 1));
+    if (h->cfg.precision >= 1 && D % 128 == 0) {      // the pose embedding runs on the fp32-split kernel, as in every low-precision handle (build_module)
+        float* q = nullptr;
+        RC(dalloc(h, &q, (size_t)D * NFS));
+        m.me_s = q;
+    }
     m.enc.resize(L);
     for (int i = 0; i < L; ++i) {
         EncLayerW& e = m.enc[i];
+        if (h->cfg.precision == 2) {                  // two fp16 planes per GEMM weight: as many bytes as the fp32 matrix
+            float* q = nullptr;
+            RC(dalloc(h, &q, (size_t)3 * D * D)); e.in_s = q;
+            RC(dalloc(h, &q, (size_t)D * D)); e.out_s = q;
+            RC(dalloc(h, &q, (size_t)F * D)); e.l1_s = q;
+            RC(dalloc(h, &q, (size_t)D * F)); e.l2_s = q;
+        }
         const std::string b = pfx + "seqTransEncoder.layers." + std::to_string(i) + ".";
         RC(add_slot(h, b + "self_attn.in_proj_weight", &e.in_w, 3 * D, D));
         RC(add_slot(h, b + "self_attn.in_proj_bias", &e.in_b, 3 * D, 1));
@@ -818,6 +832,34 @@ int encoder_layer(const Ctx& c, float* x, const EncLayerW& w, int nseq, int T, i
     return ROWOP(c, mmdm_layernorm_f32, tmp, w.n2_g, w.n2_b, x, R, D, eps, c.st);
 }
 
+// The post-norm layer on SPLIT operands (precision 2; MDMDenoiser): fp32 results from the fp16 matrix cores.  A post-norm layer uses its
+// input row as GEMM operand AND as residual, so the rows that feed a GEMM exist twice: x fp32 [R, D] (residual) and xs, their two fp16 planes [2][R][D]
+// (operand), both written by one producer -- the sequence assembly for layer 0 (mdm_pack*_planes), LN1 / LN2 afterwards (mmdm_layernorm_planes).
+//   Q|K|V = planes(xs W_in^T + b)          -> the two-plane attention (plain softmax over the T keys) -> att planes
+//   tmp   = att W_out^T + b + x            (fp32)       x, xs = LN1(tmp)
+//   f1    = planes(gelu(xs W_1^T + b))                  tmp = f1 W_2^T + b + x;  x, xs = LN2(tmp)   (last layer: x only -- nothing reads its planes)
+// Weights: the layer's fp16-plane twins (EncLayerW::*_s), in fragment order when `packed`.  rg as in encoder_layer.
+int encoder_layer_split(const Ctx& c, float* x, void* xs, const EncLayerW& w, bool packed, int nseq, int T, int D, int H, int F, float eps, void* qkv, void* att,
+                        float* tmp, void* f1, bool last, const mmdm_rag_seq* rg = nullptr, double rg_tt = 0, double rg_real = 0) {
+    const int R = rg ? rg->total_rows : nseq * T, dh = D / H;
+    const size_t RD = (size_t)R * D;
+    RC(linear_s(c, xs, D, RD, w.in_s, packed ? 0 : D, (size_t)3 * D * D, w.in_b, qkv, 3 * D, (size_t)R * 3 * D, 1, R, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0));
+    {
+        const uint16_t* q = static_cast<const uint16_t*>(qkv);
+        if (rg) RC(prof_begin(c, 1, 4.0 * (nseq / rg->items) * H * dh * rg_tt, 4.0 * (nseq / rg->items) * H * dh * 4.0 * rg_real));
+        else RC(prof_begin(c, 1, 4.0 * nseq * H * (double)T * T * dh, 4.0 * nseq * H * dh * 4.0 * T));
+        RC(mmdm_attention_planes_ex(q, 3 * D, (int64_t)R * 3 * D, q + D, 3 * D, (int64_t)R * 3 * D, 2, nullptr, 0, q + 2 * D, 3 * D, (int64_t)R * 3 * D, att, D, 2,
+                                    MMDM_ATTN_NO_ZERO_KEY, nseq, T, T, H, dh, 0, c.st, rg));
+        RC(prof_end(c, 1));
+    }
+    RC(linear_s(c, att, D, RD, w.out_s, packed ? 0 : D, (size_t)D * D, w.out_b, tmp, D, 0, 0, R, D, D, MMDM_EPI_BIAS_RESID, x, D));
+    RC(ROWOP(c, mmdm_layernorm_planes, tmp, w.n1_g, w.n1_b, x, xs, (int64_t)RD, R, D, eps, c.st));
+    RC(linear_s(c, xs, D, RD, w.l1_s, packed ? 0 : D, (size_t)F * D, w.l1_b, f1, F, (size_t)R * F, 1, R, F, D, MMDM_EPI_BIAS_GELU, nullptr, 0));
+    RC(linear_s(c, f1, F, (size_t)R * F, w.l2_s, packed ? 0 : F, (size_t)D * F, w.l2_b, tmp, D, 0, 0, R, D, F, MMDM_EPI_BIAS_RESID, x, D));
+    if (last) return ROWOP(c, mmdm_layernorm_f32, tmp, w.n2_g, w.n2_b, x, R, D, eps, c.st);
+    return ROWOP(c, mmdm_layernorm_planes, tmp, w.n2_g, w.n2_b, x, xs, (int64_t)RD, R, D, eps, c.st);
+}
+
 // MDMDenoiser.forward (mdm.py:273-298) on the CFG-doubled batch: `cond` rows are [n, ldc] with person p's latent-sized slice at
 // column p*D; sequence order person-major as in run_denoiser.
 int run_denoiser_mdm(const Ctx& c, const ModuleW& m, const float* x, int xb, int npers, int ldx, int n, int T, const float* cond, int ldc,
@@ -830,7 +872,34 @@ int run_denoiser_mdm(const Ctx& c, const ModuleW& m, const float* x, int xb, int
     for (int p = 0; p < npers; ++p)
         for (int rep = 0; rep < n / xb; ++rep)
             RC(embed(c, m, S.xp, p, S.att + c.rows_of(p * n + rep * xb, T) * D, xb, T, 1));
-    if (c.rag()) {
+    // precision 2: the split operand form of the encoder (encoder_layer_split).  Buffers of the handle's scratch set: x = S.h (fp32), its planes in S.xn,
+    // Q|K|V planes in S.qkv, attention planes in S.att (free once the assembly has read the pose embeddings), fp32 sub-layer output in S.kv, GELU planes in S.f1
+    const bool split = c.h->cfg.precision == 2;
+    const int Lm = m.st.L;
+    if (split && c.rag()) {
+        const Geom& g = *c.g;
+        if (!g.tk.rows) return mmdm_set_error(MMDM_ERR_STATE, "ragged MDM denoiser: the call has no token maps");
+        const int groups = nseq / g.B;
+        const size_t RD = (size_t)groups * g.tk.rows * D;
+        const mmdm_rag_seq tseq{g.tok_seq_off, g.tok_seq_len, groups * g.tk.rows, T + 1, g.item_order, g.B};
+        RC(ROWOP(c, mmdm_mdm_pack_rag_planes, S.att, cond, ldc, m.time_tab, c.h->d_step, m.pe, S.h, S.xn, (int64_t)RD, groups, n / g.B, D, g.rg, g.tk, c.st));
+        // the attention writes the rows of the sequences only: the padding token rows of its output planes are zeroed once (S.att held fp32 embeddings)
+        HIPCHK(hipMemsetAsync(S.att, 0, RD * 2 * sizeof(uint16_t), c.st));
+        for (int l = 0; l < Lm; ++l)
+            RC(encoder_layer_split(c, S.h, S.xn, m.enc[l], m.st.w_packed, nseq, T + 1, D, m.st.H, m.st.F, 1e-5f, S.qkv, S.att, S.kv, S.f1, l + 1 == Lm, &tseq, g.tok_tt,
+                                   (double)g.real_rows + g.B));
+        RC(ROWOP(c, mmdm_mdm_unpack_rag, S.h, S.att, groups, D, g.rg, g.tk, c.st));
+    } else if (split) {
+        const size_t RD = (size_t)nseq * (T + 1) * D;
+        for (int p = 0; p < npers; ++p) {
+            const size_t o = (size_t)p * n * (T + 1) * D;
+            RC(ROWOP(c, mmdm_mdm_pack_planes, S.att + (size_t)p * n * T * D, cond + (size_t)p * D, ldc, m.time_tab, c.h->d_step, m.pe, S.h + o,
+                     reinterpret_cast<uint16_t*>(S.xn) + o, (int64_t)RD, n, T, D, c.st));
+        }
+        for (int l = 0; l < Lm; ++l)
+            RC(encoder_layer_split(c, S.h, S.xn, m.enc[l], m.st.w_packed, nseq, T + 1, D, m.st.H, m.st.F, 1e-5f, S.qkv, S.att, S.kv, S.f1, l + 1 == Lm));
+        RC(ROWOP(c, mmdm_mdm_unpack, S.h, S.att, nseq, T, D, c.st));
+    } else if (c.rag()) {
         const Geom& g = *c.g;
         if (!g.tk.rows) return mmdm_set_error(MMDM_ERR_STATE, "ragged MDM denoiser: the call has no token maps");
         const int groups = nseq / g.B;
@@ -1119,11 +1188,17 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: bad max_batch / max_frames / text_dim");
     if (cfg->precision < 0 || cfg->precision > 3)
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: precision must be 0 (fp32 MFMA), 1 (bf16 GEMM operands), 2 (fp32 by exact bf16 operand splitting) or 3 (bf16 + fp8 QKV/FFN operands)");
+    // (MDM first: a refused mode or head size is named as such, whatever the sizes' divisibility)
+    if ((cfg->precision == 1 || cfg->precision == 3) && mdm)
+        return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_create: precision %d (%s) does not cover MDMDenoiser (model1_kind = 1): fp32_split (2) and fp32 (0) are the modes that cover MDM",
+                              cfg->precision, cfg->precision == 1 ? "bf16" : "bf16_fp8");
+    if (cfg->precision == 2 && mdm && D1 / H1 != 64 && D1 / H1 != 128)
+        return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_create: MDMDenoiser in fp32_split (precision 2) with head size %d: the two-plane attention of its encoder covers head sizes 64 and 128 (fp32 covers every size)",
+                              D1 / H1);
     if (cfg->precision == 3 && ((D % 64) || (F % 64) || (D1 % 64) || (F1 % 64) || (has_mx && ((cfg->m_latent % 64) || (cfg->m_ff % 64)))))
         return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_create: the fp8 path needs latent and ff sizes that are multiples of 64");
     if (cfg->precision >= 1 && ((D % 32) || (F % 32) || (D1 % 32) || (F1 % 32) || (has_mx && ((cfg->m_latent % 32) || (cfg->m_ff % 32)))))
         return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_create: the bf16 path needs latent and ff sizes that are multiples of 32");
-    if (cfg->precision >= 1 && mdm) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_create: the bf16 / fp32-split paths do not cover MDMDenoiser");
     RC(mmdm_kernels_init());
     mmdm_handle h = new mmdm_handle_s();
     h->cfg = *cfg;
@@ -1346,7 +1421,8 @@ extern "C" int mmdm_prepare(mmdm_handle h) {
         for (ModuleW* m : {&h->d1, &h->d2, &h->mx}) {
             StackW& st = m->st;
             const int gran = split ? 128 : 256;             // the packed kernels' N / K granularity (gemm_split.hip: 128 x 128 tiles; gemm_bf16.hip: 128 x 256, K step 128 bytes)
-            st.w_packed = !no_pack && !st.layers_b.empty() && st.D % gran == 0 && st.F % gran == 0;
+            // (MDMDenoiser, precision 2: its encoder layers' twins follow the same rule)
+            st.w_packed = !no_pack && (!st.layers_b.empty() || (split && m->kind == 1 && !m->enc.empty())) && st.D % gran == 0 && st.F % gran == 0;
             if (st.w_packed) tmp_elems = std::max(tmp_elems, (size_t)(split ? MMDM_SPLIT_NPL : 1) * std::max(3 * st.D, st.F) * st.D);
         }
         if (tmp_elems) HIPCHK(hipMalloc(&tmp, tmp_elems * 2));
@@ -1401,6 +1477,16 @@ extern "C" int mmdm_prepare(mmdm_handle h) {
                 if (!rc && st.has_ca) rc = conv(lw.ca_out_w, lb.ca_out_w, D * D, D);
                 if (rc) return herr(h, rc);
             }
+            // the post-norm encoder of MDMDenoiser (precision 2 only: mmdm_create refuses the others): the four GEMM weights of every layer
+            if (split && m->kind == 1)
+                for (EncLayerW& e : m->enc) {
+                    const int64_t D = st.D, F = st.F;
+                    int rc = conv(e.in_w, e.in_s, 3 * D * D, D);
+                    if (!rc) rc = conv(e.out_w, e.out_s, D * D, D);
+                    if (!rc) rc = conv(e.l1_w, e.l1_s, F * D, D);
+                    if (!rc) rc = conv(e.l2_w, e.l2_s, D * F, F);
+                    if (rc) return herr(h, rc);
+                }
         }
         // motion_embed [D, NFP] fp32 -> zero-padded [D, NFS] -> two fp16 planes (-> fragment order unless MMDM_NO_PACK)
         for (ModuleW* m : {&h->d1, &h->d2, &h->mx}) {

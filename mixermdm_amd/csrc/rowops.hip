@@ -194,6 +194,57 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 }
 
+// The same LayerNorm for the fp32-split post-norm encoder (MDMDenoiser, precision 2): a post-norm layer uses its normalised row twice -- as the
+// residual of the next sub-layer (fp32) and as the next GEMM's A operand (the two fp16 planes h = fp16(y), l = fp16((y - h) * 2048): kernels.h) --
+// so ONE pass reads the fp32 row, keeps it in registers (as adaln_kernel's OMODE 2 does) and writes the fp32 row and both planes.  The arithmetic
+// of y is layernorm_kernel's, statement for statement: out is bitwise that kernel's, the planes are bitwise mmdm_split2 of it.
+// planes: [2][rows][D] fp16, plane stride in elements.  In place (out == x) allowed.
+template <int MAXV>
+__global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               float* __restrict__ out, _Float16* __restrict__ planes, size_t plane, int rows, int D, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int nv = D >> 2;
+    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += gridDim.x * 4) {
+    const float* xp = x + (size_t)row * D;
+    f32x4 v[MAXV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < nv) v[i] = *reinterpret_cast<const f32x4*>(xp + 4 * c);
+        s += v[i].x + v[i].y + v[i].z + v[i].w;
+    }
+    const float mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nv) {
+            const f32x4 d = v[i] - mean;
+            q += d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
+        }
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nv) {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 4 * c);
+            const f32x4 y = (v[i] - mean) * rstd * g + b;
+            *reinterpret_cast<f32x4*>(out + (size_t)row * D + 4 * c) = y;
+            mmdm_h4 oh, ol;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const _Float16 t = mmdm_split_hi(y[e]); oh[e] = t; ol[e] = mmdm_split_lo(y[e], t); }
+            _Float16* op = planes + (size_t)row * D + 4 * c;
+            *reinterpret_cast<mmdm_h4*>(op) = oh;
+            *reinterpret_cast<mmdm_h4*>(op + plane) = ol;
+        }
+    }
+    }
+}
+
 // MDMDenoiser sequence assembly (src/models/mdm.py:279-294): dst [nseq, T+1, D];
 //   dst[s, 0, :]   = (cond[s, :] + time_tab[*step, :]) + pe[0, :]         (the conditioning token; cond row stride ldc)
 //   dst[s, 1+t, :] = src[s, t, :]                                          (pose embeddings, already + pe[1+t])
@@ -238,6 +289,65 @@ __global__ void mdm_pack_rag_kernel(const float* __restrict__ src, const float* 
         else y = src[((size_t)g * fr.rows + fr.item_off[item] + (pos - 1)) * D + d];
     }
     dst[i] = y;
+}
+
+// mdm_pack_kernel / mdm_pack_rag_kernel for the fp32-split encoder (precision 2): the assembled rows are layer 0's residual (fp32, dst) AND the A operand
+// of its QKV GEMM, so the same pass writes their two fp16 planes (planes [2][rows][D], plane stride in elements).  Four columns per thread (D % 4 == 0;
+// every row of src / cond / time_tab / pe / dst starts on a 16-byte boundary): one 16-byte load, one 16-byte and two 8-byte stores.  The token's sum keeps
+// mdm_pack_kernel's association order, so dst is bitwise that kernel's; padding token rows of the ragged form are zeros in dst and in both planes.
+__device__ __forceinline__ void store_row4_split(float* __restrict__ dst, _Float16* __restrict__ planes, size_t plane, size_t i, const f32x4 y) {
+    *reinterpret_cast<f32x4*>(dst + i) = y;
+    mmdm_h4 oh, ol;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const _Float16 t = mmdm_split_hi(y[e]); oh[e] = t; ol[e] = mmdm_split_lo(y[e], t); }
+    *reinterpret_cast<mmdm_h4*>(planes + i) = oh;
+    *reinterpret_cast<mmdm_h4*>(planes + plane + i) = ol;
+}
+
+__global__ void mdm_pack_split_kernel(const float* __restrict__ src, const float* __restrict__ cond, int ldc, const float* __restrict__ time_tab,
+                                      const int* __restrict__ step_idx, const float* __restrict__ pe, float* __restrict__ dst, _Float16* __restrict__ planes,
+                                      size_t plane, int nseq, int T, int D) {
+    const int nv = D >> 2;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (size_t)nseq * (T + 1) * nv) return;
+    const int d = 4 * (int)(j % nv);
+    const size_t row = j / nv;
+    const int t = (int)(row % (T + 1));
+    const size_t s = row / (T + 1);
+    f32x4 y;
+    if (t == 0) {
+        const f32x4 c = *reinterpret_cast<const f32x4*>(cond + s * ldc + d);
+        const f32x4 tt = *reinterpret_cast<const f32x4*>(time_tab + (size_t)(*step_idx) * D + d);
+        const f32x4 p0 = *reinterpret_cast<const f32x4*>(pe + d);
+        y = (c + tt) + p0;
+    } else {
+        y = *reinterpret_cast<const f32x4*>(src + (s * T + (t - 1)) * D + d);
+    }
+    store_row4_split(dst, planes, plane, row * D + d, y);
+}
+
+__global__ void mdm_pack_rag_split_kernel(const float* __restrict__ src, const float* __restrict__ cond, int ldc, const float* __restrict__ time_tab,
+                                          const int* __restrict__ step_idx, const float* __restrict__ pe, float* __restrict__ dst, _Float16* __restrict__ planes,
+                                          size_t plane, int groups, int gpp, int D, mmdm_rag fr, mmdm_rag tk) {
+    const int nv = D >> 2;
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (size_t)groups * tk.rows * nv) return;
+    const int d = 4 * (int)(j % nv);
+    const size_t row = j / nv;
+    const int r = (int)(row % tk.rows), g = (int)(row / tk.rows);
+    const int item = tk.row_item[r], pos = tk.row_pos[r];
+    f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (item >= 0) {
+        if (pos == 0) {
+            const f32x4 c = *reinterpret_cast<const f32x4*>(cond + ((size_t)(g % gpp) * tk.B + item) * ldc + (size_t)(g / gpp) * D + d);
+            const f32x4 tt = *reinterpret_cast<const f32x4*>(time_tab + (size_t)(*step_idx) * D + d);
+            const f32x4 p0 = *reinterpret_cast<const f32x4*>(pe + d);
+            y = (c + tt) + p0;
+        } else {
+            y = *reinterpret_cast<const f32x4*>(src + ((size_t)g * fr.rows + fr.item_off[item] + (pos - 1)) * D + d);
+        }
+    }
+    store_row4_split(dst, planes, plane, row * D + d, y);
 }
 
 // dst[g, r, :] = src[g, tk.item_off[item] + 1 + pos, :] for frame row r = (item, pos) of a group; padding frame rows are written as zeros
@@ -419,6 +529,40 @@ extern "C" int RO(mmdm_layernorm_f32)(const float* x, const float* gamma, const 
     return mmdm_check_launch("layernorm");
 }
 
+// LayerNorm into the fp32 row AND its two fp16 planes (layernorm_split_kernel); the argument rules of mmdm_layernorm_f32, plus 16-byte aligned planes
+int RO(mmdm_layernorm_planes)(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
+                              hipStream_t st) {
+    if (rows == 0) return MMDM_OK;
+    if (!x || !gamma || !beta || !out || !planes || rows < 0 || D <= 0 || !(eps > 0.f))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_split: bad arguments rows=%d D=%d", rows, D);
+    if ((D & 3) || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(out)) & 15))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_split: D must be a multiple of 4 and pointers 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(planes) & 15) || (plane_stride & 7) || plane_stride < (int64_t)rows * D)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_split: the planes must be 16-byte aligned, with a plane stride >= rows * D that is a multiple of 8 (stride=%lld)",
+                              (long long)plane_stride);
+    if (D > 64 * 4 * 8) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_layernorm_split: D=%d > 2048", D);
+    dim3 grid(min((rows + 3) / 4, 2048)), block(256);          // persistent wave slots, as mmdm_layernorm_f32
+    _Float16* pl = static_cast<_Float16*>(planes);
+    const size_t ps = (size_t)plane_stride;
+    if (D <= 256) hipLaunchKernelGGL((layernorm_split_kernel<1>), grid, block, 0, st, x, gamma, beta, out, pl, ps, rows, D, eps);
+    else if (D <= 512) hipLaunchKernelGGL((layernorm_split_kernel<2>), grid, block, 0, st, x, gamma, beta, out, pl, ps, rows, D, eps);
+    else if (D <= 1024) hipLaunchKernelGGL((layernorm_split_kernel<4>), grid, block, 0, st, x, gamma, beta, out, pl, ps, rows, D, eps);
+    else hipLaunchKernelGGL((layernorm_split_kernel<8>), grid, block, 0, st, x, gamma, beta, out, pl, ps, rows, D, eps);
+    return mmdm_check_launch("layernorm_split");
+}
+
+#ifndef MMDM_ROWOPS_NOPK
+// build: 0 = this object's kernels (the bits of mmdm_layernorm_f32), 1 = the second build's (no packed-fp32 instructions, DPP reductions: what a
+// precision-2 handle runs).  planes == NULL: the plain LayerNorm of that build.
+extern "C" int mmdm_layernorm_split(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
+                                    int build, void* stream) {
+    if (build != 0 && build != 1) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_split: build must be 0 or 1");
+    if (!planes) return build ? mmdm_layernorm_f32_nopk(x, gamma, beta, out, rows, D, eps, stream) : mmdm_layernorm_f32(x, gamma, beta, out, rows, D, eps, stream);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return build ? mmdm_layernorm_planes_nopk(x, gamma, beta, out, planes, plane_stride, rows, D, eps, st) : mmdm_layernorm_planes(x, gamma, beta, out, planes, plane_stride, rows, D, eps, st);
+}
+#endif
+
 int RO(mmdm_mdm_pack)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
                   int nseq, int T, int D, hipStream_t st) {
     const size_t n = (size_t)nseq * (T + 1) * D;
@@ -440,6 +584,31 @@ int RO(mmdm_mdm_pack_rag)(const float* src, const float* cond, int ldc, const fl
     if (n == 0) return MMDM_OK;
     hipLaunchKernelGGL(mdm_pack_rag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, fr, tk);
     return mmdm_check_launch("mdm_pack_rag");
+}
+
+// the two assembly passes with the rows' fp16 planes as a second output (precision 2: mdm_pack_split_kernel / mdm_pack_rag_split_kernel)
+int RO(mmdm_mdm_pack_planes)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                             int64_t plane_stride, int nseq, int T, int D, hipStream_t st) {
+    const size_t n = (size_t)nseq * (T + 1) * (D >> 2);
+    if (n == 0) return MMDM_OK;
+    if ((D & 3) || (ldc & 3) || (plane_stride & 7) || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(cond) | reinterpret_cast<uintptr_t>(time_tab) |
+                                                      reinterpret_cast<uintptr_t>(pe) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(planes)) & 15))
+        return mmdm_set_error(MMDM_ERR_ARG, "mdm_pack (split): D and the cond stride must be multiples of 4 and every row 16-byte aligned (D=%d ldc=%d)", D, ldc);
+    hipLaunchKernelGGL(mdm_pack_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst,
+                       static_cast<_Float16*>(planes), (size_t)plane_stride, nseq, T, D);
+    return mmdm_check_launch("mdm_pack_split");
+}
+
+int RO(mmdm_mdm_pack_rag_planes)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                                 int64_t plane_stride, int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st) {
+    const size_t n = (size_t)groups * tk.rows * (D >> 2);
+    if (n == 0) return MMDM_OK;
+    if ((D & 3) || (ldc & 3) || (plane_stride & 7) || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(cond) | reinterpret_cast<uintptr_t>(time_tab) |
+                                                      reinterpret_cast<uintptr_t>(pe) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(planes)) & 15))
+        return mmdm_set_error(MMDM_ERR_ARG, "mdm_pack_rag (split): D and the cond stride must be multiples of 4 and every row 16-byte aligned (D=%d ldc=%d)", D, ldc);
+    hipLaunchKernelGGL(mdm_pack_rag_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst,
+                       static_cast<_Float16*>(planes), (size_t)plane_stride, groups, gpp, D, fr, tk);
+    return mmdm_check_launch("mdm_pack_rag_split");
 }
 
 int RO(mmdm_mdm_unpack_rag)(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st) {

@@ -216,6 +216,7 @@ class MixerMDM(nn.Module):
         self.betas = get_named_beta_schedule(self.beta_scheduler, self.diffusion_steps)
         self.history_every = 1
         self.precision = "fp32"             # "fp32" (native fp32 MFMA, the parity path) | "fp32_split" (same accuracy, bf16 matrix cores) | "bf16"
+                                            # (MODEL1.NAME == "MDM": "fp32" or "fp32_split"; the handle refuses the bf16 modes by name)
         self.text_encoder = None            # optional callable(batch) -> cond [B, 8*768] overriding the built-in text stage
         self._text_sd, self._text_enc = None, None
         self.mixing = Mixer(self, self.mixing_mode, store_influence, cfg.FORCE_INFLUENCE_VAL, align=align)

@@ -110,6 +110,19 @@ def layernorm(x, weight, bias, eps=1e-5):
     return out
 
 
+def layernorm_split(x, weight, bias, eps=1e-5, build=0, planes=True):
+    """nn.LayerNorm with affine parameters written as fp32 rows AND as their two fp16 planes (split_f32 of the rows) in one pass
+    (mmdm_layernorm_split): returns (out fp32 like x, planes float16 [2, *x.shape]).  build: 0 = the row kernels behind `layernorm`, 1 = the build
+    without packed-fp32 instructions that fp32_split / bf16 handles run.  planes=False: the plain LayerNorm of that build, returns (out, None)."""
+    _chk(x, weight, bias)
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    D = x.shape[-1]
+    pl = torch.empty(2, *x.shape, device=x.device, dtype=torch.float16) if planes else None
+    check(load_library().mmdm_layernorm_split(_p(x), _p(weight), _p(bias), _p(out), _p(pl), x.numel(), x.numel() // D, D, float(eps), int(build), _stream()))
+    return out, pl
+
+
 def token_embed(table, tokens, pos):
     """table[tokens] + pos[:L]; tokens int32 [n, L] on the device."""
     _chk(table, tokens, pos)
@@ -383,6 +396,24 @@ def attention_split(qs, ks, vs, num_heads, kv_seq_shift=0, zero_key=True, causal
     check(load_library().mmdm_attention_split(C.c_void_p(qs.data_ptr()), qs.stride(2), qs.stride(0), C.c_void_p(ks.data_ptr()), ks.stride(2), ks.stride(0),
                                               C.c_void_p(vs.data_ptr()), vs.stride(2), vs.stride(0), C.c_void_p(out.data_ptr()), HD, 2 if split_out else 0, flags,
                                               nseq, Tq, Tk, num_heads, HD // num_heads, kv_seq_shift, _stream()))
+    return out
+
+
+def attention_split_ragged(qs, ks, vs, num_heads, seq_off, seq_len, max_len, kv_seq_shift=0, zero_key=True, causal=False, split_out=False, out=None):
+    """attention_split over a ragged batch (mmdm_attention_split_ragged): qs / ks / vs [2, rows, H*dh] torch.float16 planes (may be column slices of a
+    packed projection), sequence s = rows [seq_off[s], seq_off[s] + seq_len[s]) (int32 device tensors).  Returns fp32 [rows, H*dh] or its planes
+    [2, rows, H*dh]; rows outside every sequence are left as they are in `out` (a new tensor: uninitialised)."""
+    _chk(seq_off, seq_len)
+    for t in (qs, ks, vs):
+        assert t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.shape[0] == 2 and t.stride(2) == 1
+    assert seq_off.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_off.numel() == seq_len.numel()
+    _, rows, HD = qs.shape
+    if out is None:
+        out = torch.empty((2, rows, HD) if split_out else (rows, HD), device=qs.device, dtype=torch.float16 if split_out else torch.float32)
+    flags = (0 if zero_key else ATTN_NO_ZERO_KEY) | (ATTN_CAUSAL if causal else 0)
+    check(load_library().mmdm_attention_split_ragged(C.c_void_p(qs.data_ptr()), qs.stride(1), qs.stride(0), C.c_void_p(ks.data_ptr()), ks.stride(1), ks.stride(0),
+                                                     C.c_void_p(vs.data_ptr()), vs.stride(1), vs.stride(0), C.c_void_p(out.data_ptr()), HD, 2 if split_out else 0, flags,
+                                                     seq_off.numel(), _p(seq_off), _p(seq_len), int(max_len), rows, num_heads, HD // num_heads, kv_seq_shift, _stream()))
     return out
 
 

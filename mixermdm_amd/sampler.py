@@ -34,7 +34,8 @@ class Sampler:
         """single_only: False/0 = two-chain MixerMDM; True/1 = individual denoiser alone (2-way CFG);
         2 = interaction denoiser alone with the 4-way CFG of ClassifierFreeSampleModelMultiple;
         3 = in2IN "dual": both denoisers composed by ClassifierFreeSampleDualMDM (call set_dual_weights after set_schedule).
-        model1_kind: 0 = in2IN individual, 1 = MDMDenoiser; d1_*: denoiser1's own sizes (0 = same as d_*).
+        model1_kind: 0 = in2IN individual, 1 = MDMDenoiser (precision "fp32" or "fp32_split", the latter at head sizes 64 / 128; "bf16" /
+        "bf16_fp8" are refused for it); d1_*: denoiser1's own sizes (0 = same as d_*).
         precision: "fp32" (native fp32 MFMA), "fp32_split" (fp32 results from six bf16 MFMAs per product on exactly split operands:
         same accuracy, the bf16 matrix rate), "bf16" (bf16 GEMM operands), "bf16_fp8" (BASELINE configs[4]: as "bf16" with the QKV /
         cross-attention input projections and both FFN GEMMs on fp8 e4m3 operands)."""

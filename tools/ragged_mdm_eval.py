@@ -3,14 +3,14 @@
 
 The reference's evaluation caller samples one item at a time with that item's own length (src/evaluation/datasets.py:100-116).  bench.py --eval-items
 measures that for the in2IN MODEL1 of configs/models/MixerMDM.yaml; this script is the same measurement with MODEL1.NAME == "MDM": N items (default 16),
-T uniform in [60, 300], ddim50, fp32, on ONE model / handle: first the per-item `forward_test` loop, then `sample_many(batching="ragged")`, results
+T uniform in [60, 300], ddim50, fp32 or fp32_split (--precision), on ONE model / handle: first the per-item `forward_test` loop, then `sample_many(batching="ragged")`, results
 asserted bitwise equal, items/s of both and their ratio printed as one JSON line.
 
 MDM's sizes: no MDM YAML ships with the reference.  MDMDenoiser.text_dim is hard-coded to 256 and the cond slice is added to the latent-sized timestep
 embedding (src/models/mdm.py:238, 279), which fixes LATENT_DIM = 256; the rest are MDM's published defaults (FF_SIZE 1024, 8 layers, 4 heads: head size
 64).  The other stacks are the reference's (synthetic.FULL_DIMS).
 
-    python tools/ragged_mdm_eval.py [--items 16] [--sampler ddim50] [--profile-steps 2]
+    python tools/ragged_mdm_eval.py [--items 16] [--sampler ddim50] [--precision fp32|fp32_split] [--profile-steps 2]
 """
 import argparse
 import json
@@ -29,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=16)
     ap.add_argument("--sampler", default="ddim50")
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "fp32_split"), help="the precision modes that cover MDM as MODEL1")
     ap.add_argument("--max-rows", type=int, default=4800, help="frames per ragged batch (16 x 300)")
     ap.add_argument("--profile-steps", type=int, default=2, help="eager steps of the first ragged batch timed per kernel class (0 = none)")
     args = ap.parse_args()
@@ -45,6 +46,7 @@ def main():
         base["MODEL1"] = os.path.join(tmp, "mdm.yaml")
         base["MODEL2"] = os.path.join(ROOT, base["MODEL2"])
         model = MixerMDM(CfgNode(base), num_frames=300, sampling_strategy=args.sampler, config_root=ROOT)
+    model.precision = args.precision
     model.init_synthetic(seed=0)
     model = model.to("cuda:0").eval()
     cw = 6 * 768 + 2 * MDM["LATENT_DIM"]
@@ -69,6 +71,7 @@ def main():
     assert same, "ragged batches and the per-item loop differ"
     assert all(torch.isfinite(o).all().item() for o in got)
     line = {"metric": "evaluation items/s, MDM as MODEL1 (one forward_test per item, B = 1, %s, T uniform in [60, 300])" % args.sampler, "items": N, "frames": sum(lens),
+            "precision": args.precision,
             "model1": MDM, "sequential_forward_test": {"wall_s": round(t_seq, 3), "items_per_s": round(N / t_seq, 4)},
             "ragged": {"wall_s": round(t_rag, 3), "items_per_s": round(N / t_rag, 4)}, "ratio": round(t_seq / t_rag, 3), "bit_identical": bool(same)}
     if args.profile_steps > 0:
