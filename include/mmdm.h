@@ -252,7 +252,7 @@ int mmdm_blend_cfg_f32(const float* out1, const float* out2, const float* w, int
                        float cfg_scale, float* model_out, float* hist_i1, float* hist_i2, float* hist_mix,
                        int B, int T, void* stream);
 
-/* process_xstart + two-chain DDIM (eta = 0) update, in place on x and x2 [B,T,524]:
+/* process_xstart + two-chain DDIM (eta = 0) update, in place on x and x2 [B,T,524] (eta > 0: inside the handle, mmdm_set_eta / mmdm_begin_opts):
  *   i = *step_idx;  if i > 0: x0_1 = norm_hml(smpl_to_ih(center_motion(ih_to_smpl(m)))) per person (center only if align),
  *                             x0_2 = norm_ih(m);   else x0_1 = x0_2 = m        (m = model_out)
  *   eps = (coef[0][i]*x - x0) / coef[1][i];  x = x0*coef[2][i] + coef[3][i]*eps      (both chains)
@@ -263,6 +263,13 @@ int mmdm_blend_cfg_f32(const float* out1, const float* out2, const float* w, int
 int mmdm_xstart_ddim_f32(const float* model_out, const float* stats, const float* coef, int S, const int* step_idx,
                          float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
                          int B, int T, int align, void* stream);
+
+/* The sampler's step noise, stateless: out [B, T, 524] = the N(0, 1) values the eta > 0 update adds at loop position `loop_pos` of a call begun with
+ * noise_source = 2 and this seed (mmdm_begin_opts) -- one device function serves both.  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85), counter (t * 524 + column, b, loop_pos, 0), key (seed & 0xffffffff, seed >> 32); Box-Muller on the first two
+ * words r0, r1: u = ((r >> 8) + 0.5) 2^-24, z = sqrt(-2 log u1) cos(2 pi u2), accurate logf / cosf (for u1 >= 1/2 the logarithm is taken as
+ * log1pf(-(1 - u1)) of the exactly represented distance to one).  An element's value depends on (seed, loop_pos, b, t, column) only, never on B or T. */
+int mmdm_randn_f32(unsigned long long seed, int loop_pos, int B, int T, float* out, void* stream);
 
 /* Single-chain DDIM update (configs 1-2): x = x0*coef[2][i] + coef[3][i]*(coef[0][i]*x - x0)/coef[1][i], x0 = s*m[b] + (1-s)*m[B+b].
  * m is the denoiser output on the CFG-doubled batch [2B, T, C]; pred_xstart (optional) receives x0.
@@ -424,6 +431,15 @@ int mmdm_set_schedule(mmdm_handle h, const int* timestep_map, const float* coef,
  * step (ClassifierFreeSampleDualMDM.weight, cfg_sampler.py:113-125).  Call after every mmdm_set_schedule. */
 int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S);
 
+/* Stochastic DDIM (eta > 0; two-chain sampler only): coef_eta_host [2*S] HOST floats = sqrt(1 - ab_prev - sigma^2) and sigma of every respaced
+ * step, sigma = eta sqrt((1 - ab_prev) / (1 - ab)) sqrt(1 - ab / ab_prev) in fp32 (gaussian_diffusion.py:1939-1951); NULL clears it (S ignored)
+ * and the update is the eta = 0 one again.  Call after mmdm_set_schedule, which resets it; it ends a begun call.  While a table is set every
+ * uniform begin must name a noise source (mmdm_begin_opts; MMDM_ERR_STATE otherwise -- so mmdm_begin is refused) and mmdm_begin_ragged is
+ * MMDM_ERR_UNSUPPORTED; a noise source without a table is MMDM_ERR_STATE as well.  The step then ends in
+ *   x = x0 sqrt(ab_prev) + coef_eta[0][i] eps + [i != 0] coef_eta[1][i] noise        (both chains, the SAME noise [B, T, 524]; :1947-1963)
+ * The call waits for the stream of the handle's last begin before it replaces the table.  single_only != 0: MMDM_ERR_UNSUPPORTED. */
+int mmdm_set_eta(mmdm_handle h, const float* coef_eta_host, int S);
+
 /* Check that every weight is present; allocate nothing afterwards. */
 int mmdm_prepare(mmdm_handle h);
 
@@ -449,6 +465,37 @@ int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, 
 /* Begin a sampling call: cond [B, 8*text_dim] (layout src/models/mixermdm.py:342-354) or [B, text_dim] (single_only),
  * x_T [B,T,524] (or [B,T,262]); both chains start from x_T (gaussian_diffusion.py:1863).  Precomputes the text embeddings. */
 int mmdm_begin(mmdm_handle h, const float* cond, const float* x_T, int B, int T, void* stream);
+
+/* mmdm_begin with the loop's other arguments (MixerDiffusion.ddim_sample_loop_progressive, gaussian_diffusion.py:1822-1899); two-chain sampler,
+ * uniform batches.  A zeroed struct (or opts == NULL) is mmdm_begin.  Options belong to the CALL: every mmdm_begin / mmdm_begin_ragged resets
+ * them, as it resets the history.  Device buffers are the caller's and must stay alive until the stream has passed the call's last step.
+ *   noise_source  0 = none; 1 = `noise` [noise_steps, B, T, 524]: slot k is th.randn_like(x) of the step at loop position k (0 = the first executed
+ *                 step; the slot of the last step, i = 0, is never added: :1958-1963), noise_steps >= S - skip_timesteps; 2 = generated on the device
+ *                 from `seed`: exactly what mmdm_randn_f32(seed, loop position, B, T) writes.  Needs mmdm_set_eta (and mmdm_set_eta needs it).
+ *   x_start       [B, x_start_frames >= T, 524], normalised space: at the start of EVERY step columns 0, 2, 262, 264 (the two roots' ground path) of
+ *                 both chains are overwritten with x_start[:, :T] (:1877-1882).  pred_xstart(2) and the sample the last step leaves are not pinned.
+ *   init_image    [B, T, 524]: both chains start from init_coef[0] * init_image + init_coef[1] * x_T, init_coef = sqrt_alphas_cumprod[i0],
+ *                 sqrt_one_minus_alphas_cumprod[i0] of the first executed step i0 = S - 1 - skip_timesteps as fp32 (q_sample, :1859-1863).
+ *                 init_zeros != 0 (or skip_timesteps > 0 with no image, as the reference): an all-zero image.
+ *   skip_timesteps  the loop runs steps i0 .. 0: the step index starts at i0, the loop position (history slot, noise slot, generator counter) at 0, so
+ *                 histories hold S - skip entries.  mmdm_seek keeps its mapping (loop position S - 1 - step_index).
+ * Pointers and the seed reach the step's kernels through a device-side descriptor written on `stream`; captured graphs bake in its address and are
+ * keyed by (noise_source, x_start given) beside (B, T, S, masked): new VALUES replay the same graph, another form never does.  A key mask composes.
+ * MMDM_ERR_UNSUPPORTED: single_only 1 / 2 / 3 with any option set.  MMDM_ERR_STATE: eta table and noise source not both present / both absent.
+ * MMDM_ERR_ARG: noise_steps < S - skip_timesteps, x_start_frames < T, skip_timesteps outside [0, S); mmdm_run past the noise buffer (after mmdm_seek). */
+typedef struct {
+    int noise_source;
+    int noise_steps;
+    const float* noise;
+    unsigned long long seed;
+    const float* x_start;
+    int x_start_frames;
+    int init_zeros;
+    const float* init_image;
+    float init_coef[2];
+    int skip_timesteps;
+} mmdm_begin_options;
+int mmdm_begin_opts(mmdm_handle h, const float* cond, const float* x_T, int B, int T, const mmdm_begin_options* opts, void* stream);
 
 /* RAGGED sampling call: B items of DIFFERENT lengths in one batch -- the shape of the reference's evaluation callers, which sample one item at
  * a time with that item's own length (src/evaluation/datasets.py:58, 100-116: B = 1 or mm_num_repeats per call; per-item `motion_lens`), and
@@ -481,9 +528,10 @@ int mmdm_call_rows(mmdm_handle h, int* rows, int* real_rows, int* ragged);
  * written to a device-side descriptor on mmdm_begin's stream, so captured step graphs do not depend on them. */
 int mmdm_set_history(mmdm_handle h, float* influence_i1, float* influence_i2, float* out1, float* out2, float* out_influenced, int every);
 
-/* Run `nsteps` consecutive DDIM steps starting at the handle's current position (S-1 after mmdm_begin, counting down).
+/* Run `nsteps` consecutive DDIM steps starting at the handle's current position (S-1 after mmdm_begin, S-1-skip_timesteps after an mmdm_begin_opts
+ * that skips; counting down).
  * use_graph != 0: one step is captured into a hipGraph on first use and replayed; captured graphs are kept in a least-recently-used
- * cache keyed by (B, T, S) (8 entries; MMDM_GRAPH_CACHE=n overrides), so a caller that alternates shapes -- the evaluation loops of
+ * cache keyed by (B, T, S) and the call's form (masked, noise source, x_start given) (8 entries; MMDM_GRAPH_CACHE=n overrides), so a caller that alternates shapes -- the evaluation loops of
  * src/evaluation/datasets.py:101-122, 438 call the sampler per item with per-sample T -- re-captures nothing.
  * = MixerDiffusion.ddim_sample_loop_progressive body  gaussian_diffusion.py:1871-1899. */
 int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream);

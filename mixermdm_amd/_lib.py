@@ -42,6 +42,13 @@ class EncoderLayerWeights(C.Structure):
                                            "linear2_weight", "linear2_bias", "norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")]
 
 
+class BeginOptions(C.Structure):
+    """mmdm_begin_options (include/mmdm.h)."""
+    _fields_ = [("noise_source", C.c_int), ("noise_steps", C.c_int), ("noise", C.c_void_p), ("seed", C.c_ulonglong), ("x_start", C.c_void_p),
+                ("x_start_frames", C.c_int), ("init_zeros", C.c_int), ("init_image", C.c_void_p), ("init_coef", C.c_float * 2),
+                ("skip_timesteps", C.c_int)]
+
+
 # every symbol include/mmdm.h declares: name -> (restype, argtypes)
 _I, _VP = C.c_int, C.c_void_p
 SYMBOLS = {
@@ -96,6 +103,9 @@ SYMBOLS = {
     "mmdm_set_schedule": (_I, [_VP, _VP, _VP, _I, _VP]),
     "mmdm_prepare": (_I, [_VP]),
     "mmdm_begin": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
+    "mmdm_set_eta": (_I, [_VP, _VP, _I]),
+    "mmdm_begin_opts": (_I, [_VP, _VP, _VP, _I, _I, C.POINTER(BeginOptions), _VP]),
+    "mmdm_randn_f32": (_I, [C.c_ulonglong, _I, _I, _I, _VP, _VP]),
     "mmdm_begin_ragged": (_I, [_VP, _VP, _VP, _I, _VP, _VP]),
     "mmdm_call_rows": (_I, [_VP, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "mmdm_attention_ragged_f32": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),

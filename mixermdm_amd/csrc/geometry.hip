@@ -280,11 +280,58 @@ __device__ __forceinline__ float ddim(float x, float x0, float c0, float c1, flo
     return x0 * c2 + c3 * eps;                   // eta = 0 mean             :1949-1956
 }
 
-template <bool RAG>
+// ---------------------------------------------------------------------------------------------------------
+// Step noise of the stochastic DDIM family (eta > 0): Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+// keyed by the call's seed and counted by the element's own coordinates, so that an item's noise depends on neither B nor T.
+// One definition for the update kernel and for the stateless fill (mmdm_randn_f32).
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c[0]), l0 = 0xD2511F53u * c[0];
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c[2]), l1 = 0xCD9E8D57u * c[2];
+        c[0] = h1 ^ c[1] ^ k0; c[1] = l1; c[2] = h0 ^ c[3] ^ k1; c[3] = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// N(0, 1) of element (b, t, column) at loop position lp: counter (t * 524 + column, b, lp, 0), key (seed low, seed high); Box-Muller on
+// u = ((r >> 8) + 0.5) 2^-24 of the first two words.  (k + 0.5 has 25 significant bits once k >= 2^23: there u1 is carried as its exact
+// distance to one and the logarithm taken by log1pf, so the radius keeps its accuracy where it is small -- sqrt(2 (1 - u1)) near u1 = 1.)
+__device__ __forceinline__ float step_normal(unsigned long long seed, int lp, int b, int t, int col) {
+    uint32_t c[4] = {(uint32_t)(t * NF2 + col), (uint32_t)b, (uint32_t)lp, 0u};
+    philox4x32_10(c, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+    const uint32_t a = c[0] >> 8, g = c[1] >> 8;
+    const float lg = a < (1u << 23) ? logf(((float)a + 0.5f) * 0x1p-24f) : log1pf(-(((float)((1u << 24) - a) - 0.5f) * 0x1p-24f));
+    const float u2 = ((float)g + 0.5f) * 0x1p-24f;
+    return sqrtf(-2.0f * lg) * cosf(6.2831855f * u2);
+}
+
+__global__ __launch_bounds__(256) void randn_kernel(unsigned long long seed, int lp, int T, size_t total, float* __restrict__ out) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int col = (int)(idx % NF2);
+    const size_t fr = idx / NF2;
+    out[idx] = step_normal(seed, lp, (int)(fr / T), (int)(fr % T), col);
+}
+
+// what the NOISE forms of the update kernel take beside the plain form's arguments
+struct NoiseArgs {
+    const float* coef_eta;         // [2, S]: sqrt(1 - ab_prev - sigma^2), sigma
+    const mmdm_opts_desc* od;      // the call's noise buffer / seed (device-side: a captured graph bakes in this address only)
+    const int* loop_pos;
+};
+__device__ __forceinline__ const NoiseArgs& noise_args(const NoiseArgs& a) { return a; }
+
+// NOISE: 0 = the deterministic update (eta = 0; no extra argument: NA is empty and the kernel is what it was before the forms 1 / 2 existed),
+// 1 = + sigma * noise[loop_pos] from the caller's buffer [n_steps, B, T, 524], 2 = + sigma * step_normal(seed, loop_pos, ...).  Forms 1 / 2 read
+// sqrt(1 - ab_prev - sigma^2) and sigma from the eta table and add no noise at i = 0 (gaussian_diffusion.py:1958-1963); the same noise goes to both chains.
+template <bool RAG, int NOISE = 0, typename... NA>
 __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restrict__ m, const float* __restrict__ stats, const float* __restrict__ coef,
                                                            int S, const int* __restrict__ step_idx, float* __restrict__ x, float* __restrict__ x2,
                                                            float* __restrict__ px1, float* __restrict__ px2, const float* __restrict__ floor_ws,
-                                                           int B, int T, int align, mmdm_rag rg) {
+                                                           int B, int T, int align, mmdm_rag rg, NA... na) {
+    static_assert(NOISE == 0 ? sizeof...(NA) == 0 : (sizeof...(NA) == 1 && !RAG), "forms 1 / 2 take one NoiseArgs and are uniform-batch only");
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     int j, t, p, b;
     size_t seq;
@@ -307,7 +354,20 @@ __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restric
         seq = (size_t)b * T * NF2 + (size_t)p * NF;
     }
     const int i = *step_idx;
-    const float c0 = coef[i], c1 = coef[S + i], c2 = coef[2 * S + i], c3 = coef[3 * S + i];
+    const float c0 = coef[i], c1 = coef[S + i], c2 = coef[2 * S + i];
+    float c3, sigma = 0.f;
+    int lp = 0;
+    unsigned long long seed = 0;
+    const float* nz = nullptr;
+    if constexpr (NOISE == 0) c3 = coef[3 * S + i];
+    else {
+        const NoiseArgs& a = noise_args(na...);
+        c3 = a.coef_eta[i];
+        sigma = a.coef_eta[S + i];
+        lp = *a.loop_pos;
+        if constexpr (NOISE == 1) nz = lp < a.od->noise_steps ? a.od->noise + (size_t)lp * B * T * NF2 : nullptr;   // (the host refuses a run past the buffer)
+        else seed = a.od->seed;
+    }
     const bool norm = i > 0;                                     // `if t[0] > 0`  gaussian_diffusion.py:2052
     const float* mh = stats, *sh = stats + NF, *mi = stats + 2 * NF, *si = stats + 3 * NF;
     const size_t off = seq + (size_t)t * NF2;
@@ -374,8 +434,21 @@ __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restric
             x0b = (x0b - mi[c]) / si[c];
         }
         const size_t e = off + c;
-        x[e] = ddim(x[e], x0a, c0, c1, c2, c3);
-        x2[e] = ddim(x2[e], x0b, c0, c1, c2, c3);
+        if constexpr (NOISE == 0) {
+            x[e] = ddim(x[e], x0a, c0, c1, c2, c3);
+            x2[e] = ddim(x2[e], x0b, c0, c1, c2, c3);
+        } else {
+            float va = ddim(x[e], x0a, c0, c1, c2, c3), vb = ddim(x2[e], x0b, c0, c1, c2, c3);
+            if (i != 0) {                                        // nonzero_mask * sigma * noise, one draw for both chains   :1947, 1958-1963
+                float z;
+                if constexpr (NOISE == 1) z = nz ? nz[e] : 0.f;
+                else z = step_normal(seed, lp, b, t, p * NF + c);
+                const float sn = sigma * z;
+                va += sn; vb += sn;
+            }
+            x[e] = va;
+            x2[e] = vb;
+        }
         if (px1) px1[e] = x0a;
         if (px2) px2[e] = x0b;
     }
@@ -420,6 +493,34 @@ __global__ __launch_bounds__(256) void dual_ddim_kernel(const float* __restrict_
 
 __global__ void step_dec_kernel(int* step_idx, int* loop_pos) { *step_idx -= 1; *loop_pos += 1; }
 __global__ void set_step_kernel(int* step_idx, int* loop_pos, int s, int l) { *step_idx = s; *loop_pos = l; }
+
+// x_start of the loop (gaussian_diffusion.py:1877-1882): the ground path of both persons' roots -- columns 0, 2, 262, 264 -- of both chains is
+// overwritten with x_start[:, :T] before the models run.  x_start [B, xs_T >= T, 524] comes from the call's device-side descriptor.
+__global__ __launch_bounds__(256) void pin_root_kernel(float* __restrict__ x, float* __restrict__ x2, const mmdm_opts_desc* __restrict__ od, int B, int T) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * T * 4) return;
+    const float* xs = od->x_start;
+    const int xs_T = od->xs_T;
+    if (!xs || xs_T < T) return;
+    const int k = idx & 3, fr = idx >> 2;
+    const int col = (k >> 1) * NF + (k & 1) * 2;
+    const int b = fr / T, t = fr % T;
+    const float v = xs[((size_t)b * xs_T + t) * NF2 + col];
+    const size_t e = (size_t)fr * NF2 + col;
+    x[e] = v;
+    x2[e] = v;
+}
+
+// q_sample at the start of a call (gaussian_diffusion.py:1859-1863, 465-485): x = a * init + b * x_T on both chains (init == nullptr: zeros)
+__global__ __launch_bounds__(256) void q_sample_kernel(float* __restrict__ x, float* __restrict__ x2, const float* __restrict__ init, float a, float b, size_t total) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const float v = a * (init ? init[idx] : 0.f) + b * x[idx];
+    x[idx] = v;
+    x2[idx] = v;
+}
+
+__global__ void set_opts_kernel(mmdm_opts_desc* d, mmdm_opts_desc v) { *d = v; }
 
 // which: 0 -> hd->o1, 1 -> hd->o2; a null destination (history not requested for this call) makes the launch a no-op
 __global__ void hist_copy_kernel(const float* __restrict__ src, const mmdm_hist_desc* __restrict__ hd, int which, size_t count, const int* __restrict__ loop_pos) {
@@ -633,6 +734,49 @@ extern "C" int mmdm_xstart_ddim_f32(const float* model_out, const float* stats, 
     hipLaunchKernelGGL(xstart_ddim_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
                        pred_xstart, pred_xstart2, floor_ws, B, T, align, mmdm_rag{});
     return mmdm_check_launch("xstart_ddim");
+}
+
+// the update with step noise (form 1: the caller's buffer, 2: the device generator); uniform batches
+int mmdm_xstart_ddim_noise(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
+                           const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
+                           int B, int T, int align, hipStream_t st) {
+    if (form != 1 && form != 2) return mmdm_set_error(MMDM_ERR_ARG, "xstart_ddim_noise: form %d", form);
+    if (align) {
+        hipLaunchKernelGGL(floor_kernel<false>, dim3(B * 2), dim3(256), 0, st, model_out, floor_ws, T, mmdm_rag{});
+        if (int rc = mmdm_check_launch("floor")) return rc;
+    }
+    const int total = B * 2 * T * MMDM_NJ;
+    const NoiseArgs na{coef_eta, od, loop_pos};
+    if (form == 1)
+        hipLaunchKernelGGL((xstart_ddim_kernel<false, 1, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
+                           pred_xstart, pred_xstart2, floor_ws, B, T, align, mmdm_rag{}, na);
+    else
+        hipLaunchKernelGGL((xstart_ddim_kernel<false, 2, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
+                           pred_xstart, pred_xstart2, floor_ws, B, T, align, mmdm_rag{}, na);
+    return mmdm_check_launch("xstart_ddim_noise");
+}
+
+int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, int B, int T, hipStream_t st) {
+    hipLaunchKernelGGL(pin_root_kernel, dim3((B * T * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, B, T);
+    return mmdm_check_launch("pin_root");
+}
+
+int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st) {
+    hipLaunchKernelGGL(q_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, x2, init, a, b, total);
+    return mmdm_check_launch("q_sample");
+}
+
+int mmdm_set_opts_desc(mmdm_opts_desc* d, const mmdm_opts_desc& v, hipStream_t st) {
+    hipLaunchKernelGGL(set_opts_kernel, dim3(1), dim3(1), 0, st, d, v);
+    return mmdm_check_launch("set_opts");
+}
+
+extern "C" int mmdm_randn_f32(unsigned long long seed, int loop_pos, int B, int T, float* out, void* stream) {
+    if (B == 0 || T == 0) return MMDM_OK;
+    if (!out || B < 0 || T < 0 || loop_pos < 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_randn_f32: bad arguments");
+    const size_t total = (size_t)B * T * NF2;
+    hipLaunchKernelGGL(randn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed, loop_pos, T, total, out);
+    return mmdm_check_launch("randn");
 }
 
 // ragged batch (rg.B items, rg.rows frame rows incl. padding): same arithmetic per item

@@ -98,6 +98,20 @@ struct mmdm_hist_desc {
     int pad;
 };
 int mmdm_set_hist_desc(mmdm_hist_desc* d, const mmdm_hist_desc& v, hipStream_t st);
+// Caller buffers and the seed of the current call's options (mmdm_begin_opts), in DEVICE memory like the history destinations: the step's
+// kernels read them at run time, a captured graph bakes in the descriptor's address only.
+struct mmdm_opts_desc {
+    const float* noise;               // [noise_steps, B, T, 524] step noise, slot = loop position; null = none
+    const float* x_start;             // [B, xs_T, 524]; null = not pinned
+    unsigned long long seed;          // device generator (noise form 2)
+    int noise_steps, xs_T;
+};
+int mmdm_set_opts_desc(mmdm_opts_desc* d, const mmdm_opts_desc& v, hipStream_t st);
+int mmdm_xstart_ddim_noise(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
+                           const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
+                           int B, int T, int align, hipStream_t st);
+int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, int B, int T, hipStream_t st);
+int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st);
 int mmdm_hist_copy(const float* src, const mmdm_hist_desc* hd, int which, size_t count, const int* loop_pos, hipStream_t st);
 int mmdm_blend_cfg_dyn(const float* out1, const float* out2, const float* w, int mode, int use_force, float force, float cfg_scale,
                        float* model_out, const mmdm_hist_desc* hd, const int* loop_pos, int B, int T, hipStream_t st);

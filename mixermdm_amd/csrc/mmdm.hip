@@ -281,7 +281,15 @@ struct mmdm_handle_s {
     float *tt_stash = nullptr;                             // [3, maxD] row 0 of the three time tables while mmdm_module_forward borrows it
     float *dual_w = nullptr;                               // [Smax] DualMDM composition weight per respaced step (single_only == 3)
     bool dual_w_set = false;
-    int td1 = 0, cond_w = 0;                               // denoiser1's cond width (text_dim, or the latent size for MDM) and the cond row width
+    float *d_coef_eta = nullptr;                           // [2, Smax] sqrt(1 - ab_prev - sigma^2), sigma per respaced step (mmdm_set_eta)
+    bool eta_set = false;
+    // options of the begun call (mmdm_begin_opts): host mirror + the device-side descriptor the step's kernels read (kernels.h: mmdm_opts_desc)
+    mmdm_opts_desc opts = {nullptr, nullptr, 0ull, 0, 0};
+    mmdm_opts_desc* d_opts = nullptr;
+    int noise_form = 0;                                    // 0 = none, 1 = the caller's buffer, 2 = the device generator: which update kernel a step launches
+    bool pinned = false;                                   // x_start given: pin_root_kernel is the first node of a step
+    int host_loop = 0;                                     // mirror of loop_pos
+    int td1 = 0, cond_w = 0;                              // denoiser1's cond width (text_dim, or the latent size for MDM) and the cond row width
 
     // history: host mirror + the device-side descriptor the step's kernels read (kernels.h: mmdm_hist_desc)
     mmdm_hist_desc hist = {nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0};
@@ -298,7 +306,8 @@ struct mmdm_handle_s {
     // caller's alternating (B, T) requests (src/evaluation/datasets.py:101-122, 438) replay cached graphs instead of re-capturing.
     // (ragged calls: T = query tiles of the longest item, rows = the group stride; uniform calls: rows = 0.  Ragged calls with MDM as denoiser 1: trows =
     // the token stride, tT = query tiles of the longest token sequence -- 64 frames are one tile of frames and two of tokens; 0 otherwise)
-    struct GraphEntry { int B, T, S, rows; hipGraphExec_t exec; uint64_t used; hipEvent_t done; int masked; int trows, tT; };      // done: recorded behind the entry's last replay
+    // (noise / pinned: the call's noise form and whether it pins the roots -- other kernels, so other entries; the option VALUES are device data)
+    struct GraphEntry { int B, T, S, rows; hipGraphExec_t exec; uint64_t used; hipEvent_t done; int masked; int trows, tT; int noise, pinned; };      // done: recorded behind the entry's last replay
     std::vector<GraphEntry> graphs;
     size_t graph_cap = 8;
     uint64_t graph_clock = 0;
@@ -1037,6 +1046,8 @@ int run_step(const Ctx& c) {
         return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
     }
     const bool dual = H->cfg.single_only == 3;
+    // x_start of the call (mmdm_begin_opts): both chains' root ground paths are overwritten before the models run -- the first node of the step
+    if (H->pinned) RC(mmdm_pin_root(H->x, H->x2, H->d_opts, B, T, c.st));
     // the individual model on both persons: in2IN blocks, the "dual_individual" variant of them, or MDMDenoiser
     auto model1 = [&](const Ctx& cc) -> int {
         if (H->d1.kind == 1) return run_denoiser_mdm(cc, H->d1, H->x, B, 2, NF2, n, T, H->cond_cat + 3 * H->cfg.text_dim, H->cond_w, H->o1, NF2);
@@ -1072,6 +1083,8 @@ int run_step(const Ctx& c) {
     RC(mixer_core(c, B, T));
     if (c.rag()) RC(mmdm_xstart_ddim_rag(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
                                          H->cfg.xstart_align, c.g->rg, c.st));
+    else if (H->noise_form) RC(mmdm_xstart_ddim_noise(H->noise_form, H->model_out, H->d_stats, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts,
+                                                      H->x, H->x2, H->px1, H->px2, H->floor_ws, B, T, H->cfg.xstart_align, c.st));
     else RC(mmdm_xstart_ddim_f32(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
                                  B, T, H->cfg.xstart_align, c.st));
     return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
@@ -1310,6 +1323,11 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     h->d_hist = reinterpret_cast<mmdm_hist_desc*>(tmp);
     if (hipMemcpy(h->d_hist, &h->hist, sizeof(mmdm_hist_desc), hipMemcpyHostToDevice) != hipSuccess)
         return fail(mmdm_set_error(MMDM_ERR_HIP, "mmdm_create: history descriptor upload failed"));
+    if ((rc = dalloc(h, &h->d_coef_eta, (size_t)2 * h->Smax))) return fail(rc);
+    if ((rc = dalloc(h, &tmp, (sizeof(mmdm_opts_desc) + 3) / 4))) return fail(rc);
+    h->d_opts = reinterpret_cast<mmdm_opts_desc*>(tmp);
+    if (hipMemcpy(h->d_opts, &h->opts, sizeof(mmdm_opts_desc), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(mmdm_set_error(MMDM_ERR_HIP, "mmdm_create: options descriptor upload failed"));
     {       // key-mask buffers (mmdm_set_key_mask): up to 2 * max_batch rows (a CFG-doubled batch handed to mmdm_module_forward)
         const size_t mrows = (size_t)2 * B;
         if ((rc = dalloc(h, &tmp, (mrows * T + 3) / 4))) return fail(rc);
@@ -1540,6 +1558,7 @@ extern "C" int mmdm_set_schedule(mmdm_handle h, const int* timestep_map, const f
     h->S = S;
     h->h_tmap0 = timestep_map[0];
     h->dual_w_set = false;
+    h->eta_set = false;
     // cached step graphs stay valid: S is part of their key, the tables are device data at fixed addresses
     Ctx c{h, st, &h->sa};
     ProfPause pause(h->prof);
@@ -1559,10 +1578,46 @@ extern "C" int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S) 
     return MMDM_OK;
 }
 
-// mmdm_begin (lens == nullptr: B items of T frames) and mmdm_begin_ragged (lens = B host ints, x_T = the items' frames back to back)
-static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B, int T, const int* lens, void* stream) {
+extern "C" int mmdm_set_eta(mmdm_handle h, const float* coef_eta_host, int S) {
+    if (!h) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_eta: null handle");
+    if (h->cfg.single_only != 0)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_eta: eta > 0 covers the two-chain MixerMDM sampler (single_only = %d)", h->cfg.single_only));
+    if (h->S == 0) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_set_eta: call mmdm_set_schedule first"));
+    if (!coef_eta_host) { h->eta_set = false; h->begun = false; return MMDM_OK; }
+    if (S != h->S) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_eta: S=%d does not match the schedule (%d steps)", S, h->S));
+    // steps of an earlier call may still be queued and read the table
+    if (h->call_stream) HIPCHK(hipStreamSynchronize(h->call_stream));
+    HIPCHK(hipMemcpy(h->d_coef_eta, coef_eta_host, (size_t)2 * S * sizeof(float), hipMemcpyHostToDevice));
+    h->eta_set = true;
+    h->begun = false;
+    return MMDM_OK;
+}
+
+// mmdm_begin (lens == nullptr: B items of T frames; o: the call's options or nullptr) and mmdm_begin_ragged (lens = B host ints, x_T = the items'
+// frames back to back)
+static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B, int T, const int* lens, void* stream, const mmdm_begin_options* o = nullptr,
+                      const char* who = "mmdm_begin") {
     if (!h || !cond || !x_T) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_begin: null argument");
     if (!h->prepared || h->S == 0) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_begin: prepare() and set_schedule() first"));
+    static const mmdm_begin_options none = {};
+    if (!o) o = &none;
+    const bool any = o->noise_source || o->noise || o->x_start || o->init_image || o->init_zeros || o->skip_timesteps;
+    if (lens && h->eta_set)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: eta is set on the handle; the stochastic update covers uniform batches (clear it with mmdm_set_eta(h, NULL, 0))"));
+    if (any && h->cfg.single_only != 0)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: step noise, x_start, init_image and skip_timesteps cover the two-chain MixerMDM sampler (single_only = %d)", who, h->cfg.single_only));
+    if (o->noise_source < 0 || o->noise_source > 2 || (o->noise_source == 1 && !o->noise))
+        return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: noise_source must be 0 (none), 1 (buffer, not NULL) or 2 (seed)", who));
+    if (o->skip_timesteps < 0 || o->skip_timesteps >= h->S)
+        return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: skip_timesteps=%d outside [0, %d)", who, o->skip_timesteps, h->S));
+    if (h->eta_set && !o->noise_source)
+        return herr(h, mmdm_set_error(MMDM_ERR_STATE, "%s: eta is set on the handle and the call names no noise source (a noise buffer or a seed: mmdm_begin_opts)", who));
+    if (!h->eta_set && o->noise_source)
+        return herr(h, mmdm_set_error(MMDM_ERR_STATE, "%s: a noise source is given and no eta table is set (mmdm_set_eta after mmdm_set_schedule)", who));
+    if (o->noise_source == 1 && o->noise_steps < h->S - o->skip_timesteps)
+        return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: the noise buffer holds %d steps, %d are left in the schedule", who, o->noise_steps, h->S - o->skip_timesteps));
+    if (o->x_start && o->x_start_frames < T)
+        return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: x_start has %d frames, the call has T=%d", who, o->x_start_frames, T));
     Geom g;
     if (lens && h->mask_rows)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: a key mask is set on the handle; ragged batches carry their lengths instead (clear it with mmdm_set_key_mask(h, NULL, 0, 0))"));
@@ -1661,8 +1716,19 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
         if (h->x2) RC(load_x(h->x2, NF2));                  // img2 = img.clone()
     }
     if (rc) return herr(h, rc);
-    RC(mmdm_set_step(h->d_step, h->d_step + 1, h->S - 1, 0, st));
-    h->host_step = h->S - 1;
+    // the call's options (all defaults for mmdm_begin / mmdm_begin_ragged): like the history they belong to the call and are reset by every begin.
+    // Caller pointers and the seed go to the device-side descriptor ON THE STREAM, behind any step of the previous call still in flight
+    const int i0 = h->S - 1 - o->skip_timesteps;           // first executed step: indices = range(S - skip)[::-1]   gaussian_diffusion.py:1857
+    if (o->init_image || o->init_zeros || o->skip_timesteps)      // q_sample(init_image, i0, x_T), img2 = img.clone()   :1854-1863 (skip and no image: zeros)
+        RC(herr(h, mmdm_q_sample(h->x, h->x2, o->init_image, o->init_coef[0], o->init_coef[1], (size_t)B * T * NF2, st)));
+    h->opts = mmdm_opts_desc{o->noise_source == 1 ? o->noise : nullptr, o->x_start, o->noise_source == 2 ? o->seed : 0ull,
+                             o->noise_source == 1 ? o->noise_steps : 0, o->x_start ? o->x_start_frames : 0};
+    RC(herr(h, mmdm_set_opts_desc(h->d_opts, h->opts, st)));
+    h->noise_form = o->noise_source;
+    h->pinned = o->x_start != nullptr;
+    RC(mmdm_set_step(h->d_step, h->d_step + 1, i0, 0, st));
+    h->host_step = i0;
+    h->host_loop = 0;
     h->B = B; h->T = T; h->begun = true;
     h->geom = g;
     h->call_stream = st;
@@ -1674,6 +1740,10 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
 
 extern "C" int mmdm_begin(mmdm_handle h, const float* cond, const float* x_T, int B, int T, void* stream) {
     return begin_impl(h, cond, x_T, B, T, nullptr, stream);
+}
+
+extern "C" int mmdm_begin_opts(mmdm_handle h, const float* cond, const float* x_T, int B, int T, const mmdm_begin_options* opts, void* stream) {
+    return begin_impl(h, cond, x_T, B, T, nullptr, stream, opts, "mmdm_begin_opts");
 }
 
 extern "C" int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, void* stream) {
@@ -1710,6 +1780,8 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
     if (h->mask_rows && h->geom.rag) return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_run: a key mask is set on the handle and the begun call is ragged"));
     RC(herr(h, use_key_mask(h, c, h->B, h->T, "mmdm_run")));
     const int masked = c.kmask ? 1 : 0;
+    if (h->noise_form == 1 && h->host_loop + nsteps > h->opts.noise_steps)
+        return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_run: %d steps from loop position %d run past the call's noise buffer (%d steps)", nsteps, h->host_loop, h->opts.noise_steps));
     if (use_graph && !h->prof.on && !st) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_run: graph capture needs a non-default stream"));
     if (nsteps == 0) return MMDM_OK;
     // MMDM_SERIALIZE_HANDLES=1: this call's steps start behind the previous sampling call of any handle, and the next one behind them
@@ -1736,7 +1808,8 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
         const int kT = h->geom.rag ? (h->T + 63) / 64 : h->T, kR = h->geom.rag ? h->geom.rows : 0;
         const int kTR = h->geom.rag ? h->geom.tk.rows : 0, kTT = kTR ? (h->T + 1 + 63) / 64 : 0;
         for (auto& g : h->graphs)
-            if (g.B == h->B && g.T == kT && g.S == h->S && g.rows == kR && g.masked == masked && g.trows == kTR && g.tT == kTT) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
+            if (g.B == h->B && g.T == kT && g.S == h->S && g.rows == kR && g.masked == masked && g.trows == kTR && g.tT == kTT && g.noise == h->noise_form &&
+                g.pinned == (h->pinned ? 1 : 0)) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
         if (!exec) {
             hipGraph_t g = nullptr;
             // one capture at a time in the process: several handles may be driven from several host threads (mmdm_create_shared), and two
@@ -1770,7 +1843,7 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
                 (void)hipGraphExecDestroy(exec);
                 return herr(h, mmdm_set_error(MMDM_ERR_HIP, "mmdm_run: hipEventCreate: %s", hipGetErrorString(e)));
             }
-            h->graphs.push_back({h->B, kT, h->S, kR, exec, ++h->graph_clock, done, masked, kTR, kTT});
+            h->graphs.push_back({h->B, kT, h->S, kR, exec, ++h->graph_clock, done, masked, kTR, kTT, h->noise_form, h->pinned ? 1 : 0});
             ++h->n_captures;
             // the FIRST launch of a fresh exec binds the runtime's internal branch streams to it (hip::Graph::UpdateStreams): still inside the
             // exclusive section -- beside another thread's launch that is where the runtime was seen to crash
@@ -1790,6 +1863,7 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
         }
     }
     h->host_step -= nsteps;
+    h->host_loop += nsteps;
     return MMDM_OK;
 }
 
@@ -1799,6 +1873,7 @@ extern "C" int mmdm_seek(mmdm_handle h, int step_index, void* stream) {
     if (step_index < 0 || step_index >= h->S) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_seek: step index %d outside [0, %d)", step_index, h->S));
     RC(mmdm_set_step(h->d_step, h->d_step + 1, step_index, h->S - 1 - step_index, static_cast<hipStream_t>(stream)));
     h->host_step = step_index;
+    h->host_loop = h->S - 1 - step_index;
     return MMDM_OK;
 }
 

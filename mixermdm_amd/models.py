@@ -168,12 +168,25 @@ class MixerDiffusion:
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None, randomize_class=False,
-                         cond_fn_with_grad=False, dump_steps=None, const_noise=False, x_start=None):
+                         cond_fn_with_grad=False, dump_steps=None, const_noise=False, x_start=None, *, step_noise=None, seed=None):
+        """eta, skip_timesteps, init_image and x_start as in the reference (gaussian_diffusion.py:1854-1882, 1936-1965).  Two keyword-only arguments of
+        this port name the noise of the eta > 0 steps: step_noise [>= S - skip, B, T, 524] (slot k = th.randn_like(x) of the k-th executed step) or
+        seed (the device generator; ops.randn(seed, k, B, T) is slot k).  With eta > 0 and neither, a seed is drawn from torch's default generator:
+        torch.manual_seed reproduces a run.  At eta = 0 the noise is multiplied by zero and neither is read."""
         if dump_steps is not None or const_noise:
             raise NotImplementedError()                                   # gaussian_diffusion.py:1794-1797
-        if clip_denoised or denoised_fn is not None or cond_fn is not None or eta != 0.0 or skip_timesteps or init_image is not None \
-                or randomize_class or cond_fn_with_grad or x_start is not None:
+        if clip_denoised or denoised_fn is not None or cond_fn is not None or randomize_class or cond_fn_with_grad:
             raise NotImplementedError("HIP sampler implements the configuration MixerMDM.forward uses: clip_denoised=False, eta=0, no guidance fn")
+        eta = float(eta)
+        if eta < 0:
+            raise ValueError(f"eta={eta} must be >= 0")
+        if step_noise is not None and seed is not None:
+            raise ValueError("give the step noise as a buffer (step_noise=) or as a seed (seed=), not both")
+        if eta == 0.0:
+            step_noise = seed = None
+        elif step_noise is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        opts = dict(eta=eta, noise=step_noise, seed=seed, x_start=x_start, init_image=init_image, skip_timesteps=int(skip_timesteps))
         mixer = model.model if isinstance(model, ClassifierFreeSampleModelX2) else model
         owner = mixer._owner
         model_kwargs = model_kwargs or {}
@@ -182,7 +195,7 @@ class MixerDiffusion:
         B, T, _ = shape
         dev = owner.device
         x_T = noise if noise is not None else torch.randn(*shape, device=dev)
-        return owner._run_loop(self, cond, x_T, cfg_scale=getattr(model, "s", owner.cfg_mixing_weight), mask=mask)
+        return owner._run_loop(self, cond, x_T, cfg_scale=getattr(model, "s", owner.cfg_mixing_weight), mask=mask, opts=opts)
 
 
 class MixerMDM(nn.Module):
@@ -372,13 +385,13 @@ class MixerMDM(nn.Module):
         return self.text_encoder(batch)
 
     # ---- sampling -----------------------------------------------------------------------------------
-    def _run_loop(self, diffusion, cond, x_T, cfg_scale=None, mask=None):
+    def _run_loop(self, diffusion, cond, x_T, cfg_scale=None, mask=None, opts=None):
         B, T = x_T.shape[:2]
         smp = self._sampler_for(B, T, cfg_scale=cfg_scale)
         with _KeyMask(smp, mask):
-            return self._run_loop_on(smp, diffusion, cond, x_T)
+            return self._run_loop_on(smp, diffusion, cond, x_T, opts)
 
-    def _run_loop_on(self, smp, diffusion, cond, x_T):
+    def _run_loop_on(self, smp, diffusion, cond, x_T, opts=None):
         B, T = x_T.shape[:2]
         sch = diffusion.schedule
         # the facade builds a new MixerDiffusion per call (as the reference does, mixermdm.py:515-522): compare schedules by CONTENT so
@@ -392,22 +405,34 @@ class MixerMDM(nn.Module):
             with torch.cuda.device(smp.device):
                 check(smp.lib.mmdm_set_schedule(smp.h, tmap.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p), sch.num_timesteps, smp._s()), smp.h)
             smp.schedule, smp._strategy = sch, sch.key()
+            smp.eta = 0.0                                  # mmdm_set_schedule resets the eta table
+        opts = dict(opts or {})
+        eta = opts.pop("eta", 0.0)
+        if eta != getattr(smp, "eta", 0.0):
+            smp.set_eta(eta)
+        skip = opts.get("skip_timesteps", 0)
+        if not 0 <= skip < sch.num_timesteps:
+            raise ValueError(f"skip_timesteps={skip} outside [0, {sch.num_timesteps})")
         m = self.mixing
         names = []
         if m.store_influence:
             names += ["influence_i1", "influence_i2"]
         if m.mode == "eval":
             names += ["out1", "out2", "out_influenced"]
-        slots = (sch.num_timesteps + self.history_every - 1) // self.history_every
+        slots = (sch.num_timesteps - skip + self.history_every - 1) // self.history_every      # one entry per EXECUTED step
         wi = 262 if m.mixing_mode >= 3 else 1          # modes 1-2 keep the un-expanded [2B, T, 1] influence (mixermdm.py:739-745)
         need = slots * 2 * B * T * 4 * sum(wi if n.startswith("influence") else 524 for n in names)
         if need > HISTORY_BUDGET_BYTES:
             raise MemoryError(f"history side outputs need {need / 2**30:.1f} GiB for {sch.num_timesteps} steps (the reference keeps every step: "
                               "mixermdm.py:794-808); set model.history_every = k to keep every k-th step, or store_influence=False / forward_test")
-        smp.begin(cond, x_T)
-        hist = smp.set_history(names, self.history_every) if names else {}
-        smp.run(None, use_graph=True)
-        out = smp.state()["pred_xstart2"].clone()
+        try:
+            smp.begin(cond, x_T, **opts)
+            hist = smp.set_history(names, self.history_every) if names else {}
+            smp.run(None, use_graph=True)
+            out = smp.state()["pred_xstart2"].clone()
+        finally:
+            if eta:                                        # eta belongs to this call: the facade's other entry points find the handle as they left it
+                smp.set_eta(0.0)
         torch.cuda.current_stream(smp.device).wait_stream(smp.stream)
         as_list = lambda n: list(hist[n].unbind(0)) if n in hist else []
         m.history_influence_i1, m.history_influence_i2 = as_list("influence_i1"), as_list("influence_i2")
@@ -424,6 +449,7 @@ class MixerMDM(nn.Module):
             with torch.cuda.device(smp.device):
                 check(smp.lib.mmdm_set_schedule(smp.h, tmap.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p), sch.num_timesteps, smp._s()), smp.h)
             smp.schedule, smp._strategy = sch, sch.key()
+            smp.eta = 0.0
 
     def _pool(self, k, B, T):
         """k samplers over ONE weight set: the facade's own handle plus k - 1 handles that borrow its weights (mmdm_create_shared), each with its

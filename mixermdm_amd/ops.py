@@ -231,6 +231,18 @@ def xstart_ddim(model_out, stats, coef, step_idx, x, x2, align=True):
     return p1, p2
 
 
+def randn(seed, loop_pos, B, T, device=None):
+    """mmdm_randn_f32: [B, T, 524] = exactly the N(0, 1) values the eta > 0 sampler adds at loop position `loop_pos` of a call begun with
+    seed=`seed` (Philox4x32-10 counted by the element's own (t, column, b): independent of B and T)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("mixermdm_amd ops run on the GPU only (no CPU fallback)")
+    dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+    out = torch.empty(B, T, 524, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        check(load_library().mmdm_randn_f32(int(seed) & 0xFFFFFFFFFFFFFFFF, int(loop_pos), B, T, _p(out), _stream()))
+    return out
+
+
 def cfg_ddim(m, coef, step_idx, cfg_scale, x):
     _chk(m, coef, step_idx, x)
     B, T, Cc = x.shape

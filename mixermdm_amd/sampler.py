@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Config, load_library, check
+from ._lib import Config, BeginOptions, load_library, check
 from .schedule import make_schedule
 
 STATS_ORDER = ("mean_hml", "std_hml", "mean_ih", "std_ih")
@@ -142,7 +142,23 @@ class Sampler:
             check(self.lib.mmdm_set_schedule(self.h, tmap.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p), sch.num_timesteps, self._s()), self.h)
         self.schedule = sch
         self._strategy = sch.key()
+        self.eta = 0.0
         return sch
+
+    def set_eta(self, eta):
+        """mmdm_set_eta: the stochastic DDIM family (gaussian_diffusion.py:1939-1963), eta = 1 being DDPM-like.  Call after set_schedule (which resets
+        it to 0).  While eta > 0 every begin / sample names a noise source (noise= or seed=); eta = 0 clears the table."""
+        eta = float(eta)
+        if eta < 0:
+            raise ValueError(f"set_eta: eta={eta} must be >= 0")
+        with torch.cuda.device(self.device):
+            if eta == 0.0:
+                check(self.lib.mmdm_set_eta(self.h, None, 0), self.h)
+            else:
+                tab = np.ascontiguousarray(self.schedule.eta_coefficients(eta))
+                check(self.lib.mmdm_set_eta(self.h, tab.ctypes.data_as(C.c_void_p), self.schedule.num_timesteps), self.h)
+        self.eta = eta
+        return self
 
     def set_dual_weights(self, func, value):
         """Composition weight of ClassifierFreeSampleDualMDM (cfg_sampler.py:113-125) evaluated in float64 on the model-side
@@ -178,21 +194,63 @@ class Sampler:
         return self
 
     # ---- sampling ---------------------------------------------------------------------------------
-    def begin(self, cond, x_T):
+    def begin(self, cond, x_T, *, noise=None, seed=None, x_start=None, init_image=None, skip_timesteps=0):
+        """mmdm_begin, or mmdm_begin_opts when a keyword is given (the other arguments of MixerDiffusion.ddim_sample_loop, two-chain sampler):
+        noise [n >= S - skip, B, T, 524] = the step noises by loop position, or seed = the device generator's (ops.randn(seed, k, B, T) is step k's
+        noise) -- one of them while eta > 0 (set_eta); x_start [B, T' >= T, 524] pins the roots' ground path at every step; init_image [B, T, 524] /
+        skip_timesteps start the chains from q_sample(init_image, S - 1 - skip, x_T) (skip > 0 and no image: zeros) and run the steps from there."""
         cond = cond.to(self.device, torch.float32).contiguous()
         x_T = x_T.to(self.device, torch.float32).contiguous()
         B, T = x_T.shape[:2]
+        S = self.schedule.num_timesteps
+        skip = int(skip_timesteps)
+        keep = [cond, x_T]
+        opts = None
+        if noise is not None or seed is not None or x_start is not None or init_image is not None or skip:
+            if noise is not None and seed is not None:
+                raise ValueError("begin: give the step noise as a buffer (noise=) or as a seed (seed=), not both")
+            opts = BeginOptions()
+            dev32 = lambda t: t.to(self.device, torch.float32).contiguous()
+            if noise is not None:
+                noise = dev32(noise)
+                if noise.dim() != 4 or tuple(noise.shape[1:]) != (B, T, 524):
+                    raise ValueError(f"begin: noise [steps, {B}, {T}, 524] expected, got {tuple(noise.shape)}")
+                opts.noise_source, opts.noise, opts.noise_steps = 1, noise.data_ptr(), noise.shape[0]
+                keep.append(noise)
+            elif seed is not None:
+                opts.noise_source, opts.seed = 2, int(seed) & 0xFFFFFFFFFFFFFFFF
+            if x_start is not None:
+                x_start = dev32(x_start)
+                if x_start.dim() != 3 or x_start.shape[0] != B or x_start.shape[2] != 524:
+                    raise ValueError(f"begin: x_start [{B}, T' >= {T}, 524] expected, got {tuple(x_start.shape)}")
+                opts.x_start, opts.x_start_frames = x_start.data_ptr(), x_start.shape[1]
+                keep.append(x_start)
+            if init_image is not None:
+                init_image = dev32(init_image)
+                if tuple(init_image.shape) != (B, T, 524):
+                    raise ValueError(f"begin: init_image [{B}, {T}, 524] expected, got {tuple(init_image.shape)}")
+                opts.init_image = init_image.data_ptr()
+                keep.append(init_image)
+            opts.skip_timesteps = skip
+            if (init_image is not None or skip) and 0 <= skip < S:
+                a, b = self.schedule.q_sample_coefficients(S - 1 - skip)
+                opts.init_coef[0], opts.init_coef[1] = float(a), float(b)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         # the copies into the handle run on the sampler's stream, possibly long after this call returns (several calls in flight):
         # keep the allocator from handing the inputs' memory out again before that stream has passed this point
-        cond.record_stream(self.stream)
-        x_T.record_stream(self.stream)
+        for t in keep:
+            t.record_stream(self.stream)
         with torch.cuda.device(self.device):
-            check(self.lib.mmdm_begin(self.h, C.c_void_p(cond.data_ptr()), C.c_void_p(x_T.data_ptr()), B, T, self._s()), self.h)
-        self._keep = (cond, x_T)
+            if opts is None:
+                check(self.lib.mmdm_begin(self.h, C.c_void_p(cond.data_ptr()), C.c_void_p(x_T.data_ptr()), B, T, self._s()), self.h)
+            else:
+                check(self.lib.mmdm_begin_opts(self.h, C.c_void_p(cond.data_ptr()), C.c_void_p(x_T.data_ptr()), B, T, C.byref(opts), self._s()), self.h)
+        self._keep = tuple(keep)
         self.B, self.T = B, T
         self.lens, self.rows = None, B * T
         self._hist = None
+        self._left = S - skip
+        self._steps = S - skip
         return self
 
     def begin_ragged(self, cond, x_T, lens):
@@ -218,6 +276,7 @@ class Sampler:
         self.B, self.T = B, max(lens)
         self.lens, self.rows = lens, rows.value
         self._hist = None
+        self._left = self._steps = self.schedule.num_timesteps
         return self
 
     def item_slices(self):
@@ -231,8 +290,9 @@ class Sampler:
     def set_history(self, names=("influence_i1", "influence_i2", "out1", "out2", "out_influenced"), every=1):
         """Allocate history buffers [slots, 2B, T, C] for the requested side outputs (mixermdm.py:794-796, 805-808).  C = 524 for
         out1 / out2 / out_influenced; for the influences 262 in mixing modes 3-4 and 1 in modes 1-2 (the reference's shapes).
-        Ragged call: [slots, 2, rows, C] -- cond half, uncond half, each a group of the call's frame rows (item_slices())."""
-        S = self.schedule.num_timesteps
+        Ragged call: [slots, 2, rows, C] -- cond half, uncond half, each a group of the call's frame rows (item_slices()).  A call begun with
+        skip_timesteps executes S - skip steps and keeps as many entries, as the reference does."""
+        S = getattr(self, "_steps", None) or self.schedule.num_timesteps
         slots = (S + every - 1) // every
         n = 2 * self.B
         bufs = {}
@@ -250,16 +310,21 @@ class Sampler:
         return bufs
 
     def run(self, nsteps=None, use_graph=True):
+        """nsteps=None: the steps that are left (all S after a plain begin; S - skip_timesteps after a begin that skips; step_index + 1 after seek)."""
         if nsteps is None:
-            nsteps = self.schedule.num_timesteps
+            left = getattr(self, "_left", None)
+            nsteps = self.schedule.num_timesteps if left is None else left
         with torch.cuda.device(self.device):
             check(self.lib.mmdm_run(self.h, nsteps, int(use_graph), self._s()), self.h)
+        if getattr(self, "_left", None) is not None:
+            self._left -= nsteps
         return self
 
     def seek(self, step_index):
         """Continue the begun call from respaced step `step_index` (S-1 = first, 0 = last) with the chains as they stand."""
         with torch.cuda.device(self.device):
             check(self.lib.mmdm_seek(self.h, int(step_index), self._s()), self.h)
+        self._left = int(step_index) + 1
         return self
 
     def synchronize(self):
@@ -279,9 +344,13 @@ class Sampler:
             out[nm] = _from_ptr(p.value, shape, self.device) if p.value else None
         return out
 
-    def sample(self, cond, x_T, use_graph=True, history=None, history_every=1):
-        """Full loop: MixerDiffusion.ddim_sample_loop (gaussian_diffusion.py:1769-1820) -> last pred_xstart2 (or pred_xstart, single)."""
-        self.begin(cond, x_T)
+    def sample(self, cond, x_T, use_graph=True, history=None, history_every=1, *, eta=None, noise=None, seed=None, x_start=None, init_image=None,
+               skip_timesteps=0):
+        """Full loop: MixerDiffusion.ddim_sample_loop (gaussian_diffusion.py:1769-1820) -> last pred_xstart2 (or pred_xstart, single).
+        eta: None = as set_eta left it; a number = set_eta(eta) first (it stays set).  The other keywords are begin()'s."""
+        if eta is not None and float(eta) != getattr(self, "eta", 0.0):
+            self.set_eta(eta)
+        self.begin(cond, x_T, noise=noise, seed=seed, x_start=x_start, init_image=init_image, skip_timesteps=skip_timesteps)
         hist = self.set_history(history, history_every) if history else None
         self.run(None, use_graph)
         st = self.state()
@@ -320,6 +389,7 @@ class Sampler:
             check(self.lib.mmdm_run(self.h, self.schedule.num_timesteps, int(use_graph), self._s()), self.h)
             check(self.lib.mmdm_copy_result(self.h, C.c_void_p(out.data_ptr()), self._s()), self.h)
         self.B, self.T, self.lens, self.rows = B, T, None, B * T
+        self._left, self._steps = 0, self.schedule.num_timesteps
 
     def sample_ragged_async(self, cond, x_T, lens, use_graph=True, history=None, history_every=1):
         """A whole ragged sampling call queued on the sampler's stream (no host synchronisation): -> (list of per-item results [T_i, C], history

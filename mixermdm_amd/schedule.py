@@ -108,6 +108,21 @@ class RespacedSchedule:
                          np.sqrt(ab_prev),
                          np.sqrt(one - ab_prev - np.float32(0.0) ** 2)]).astype(np.float32)
 
+    def eta_coefficients(self, eta):
+        """[2, S] fp32: sqrt(1 - ab_prev - sigma^2), sigma of the stochastic DDIM family (gaussian_diffusion.py:1939-1951), in the
+        reference's fp32 operation order on the fp32-cast tables: sigma = eta * sqrt((1 - ab_prev) / (1 - ab)) * sqrt(1 - ab / ab_prev).
+        eta = 0: row 0 is row 3 of device_coefficients(), row 1 is zero."""
+        ab = self.alphas_cumprod.astype(np.float32)
+        ab_prev = self.alphas_cumprod_prev.astype(np.float32)
+        one = np.float32(1.0)
+        sigma = np.float32(eta) * np.sqrt((one - ab_prev) / (one - ab)) * np.sqrt(one - ab / ab_prev)
+        return np.stack([np.sqrt(one - ab_prev - sigma * sigma), sigma]).astype(np.float32)
+
+    def q_sample_coefficients(self, i):
+        """(sqrt_alphas_cumprod[i], sqrt_one_minus_alphas_cumprod[i]) as q_sample reads them: float64 tables (gaussian_diffusion.py:354-355)
+        cast to fp32 by _extract_into_tensor."""
+        return (np.float32(np.sqrt(self.alphas_cumprod)[i]), np.float32(np.sqrt(1.0 - self.alphas_cumprod)[i]))
+
 
 def make_schedule(beta_scheduler="cosine", diffusion_steps=1000, sampling_strategy="ddim50"):
     return RespacedSchedule(get_named_beta_schedule(beta_scheduler, diffusion_steps),
