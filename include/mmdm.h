@@ -434,8 +434,9 @@ int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S);
 /* Stochastic DDIM (eta > 0; two-chain sampler only): coef_eta_host [2*S] HOST floats = sqrt(1 - ab_prev - sigma^2) and sigma of every respaced
  * step, sigma = eta sqrt((1 - ab_prev) / (1 - ab)) sqrt(1 - ab / ab_prev) in fp32 (gaussian_diffusion.py:1939-1951); NULL clears it (S ignored)
  * and the update is the eta = 0 one again.  Call after mmdm_set_schedule, which resets it; it ends a begun call.  While a table is set every
- * uniform begin must name a noise source (mmdm_begin_opts; MMDM_ERR_STATE otherwise -- so mmdm_begin is refused) and mmdm_begin_ragged is
- * MMDM_ERR_UNSUPPORTED; a noise source without a table is MMDM_ERR_STATE as well.  The step then ends in
+ * begin must name a noise source (mmdm_begin_opts, or mmdm_begin_ragged_opts for a ragged batch; MMDM_ERR_STATE otherwise -- so mmdm_begin is refused;
+ * the option-less mmdm_begin_ragged is MMDM_ERR_UNSUPPORTED and points at mmdm_begin_ragged_opts); a noise source without a table is MMDM_ERR_STATE as
+ * well.  The step then ends in
  *   x = x0 sqrt(ab_prev) + coef_eta[0][i] eps + [i != 0] coef_eta[1][i] noise        (both chains, the SAME noise [B, T, 524]; :1947-1963)
  * The call waits for the stream of the handle's last begin before it replaces the table.  single_only != 0: MMDM_ERR_UNSUPPORTED. */
 int mmdm_set_eta(mmdm_handle h, const float* coef_eta_host, int S);
@@ -467,7 +468,7 @@ int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, 
 int mmdm_begin(mmdm_handle h, const float* cond, const float* x_T, int B, int T, void* stream);
 
 /* mmdm_begin with the loop's other arguments (MixerDiffusion.ddim_sample_loop_progressive, gaussian_diffusion.py:1822-1899); two-chain sampler,
- * uniform batches.  A zeroed struct (or opts == NULL) is mmdm_begin.  Options belong to the CALL: every mmdm_begin / mmdm_begin_ragged resets
+ * uniform batches (ragged ones: mmdm_begin_ragged_opts).  A zeroed struct (or opts == NULL) is mmdm_begin.  Options belong to the CALL: every mmdm_begin / mmdm_begin_ragged resets
  * them, as it resets the history.  Device buffers are the caller's and must stay alive until the stream has passed the call's last step.
  *   noise_source  0 = none; 1 = `noise` [noise_steps, B, T, 524]: slot k is th.randn_like(x) of the step at loop position k (0 = the first executed
  *                 step; the slot of the last step, i = 0, is never added: :1958-1963), noise_steps >= S - skip_timesteps; 2 = generated on the device
@@ -516,6 +517,37 @@ int mmdm_begin_opts(mmdm_handle h, const float* cond, const float* x_T, int B, i
  * fp32-split: the precisions MDM has); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
  * otherwise MMDM_ERR_UNSUPPORTED / MMDM_ERR_ARG.  mmdm_run / mmdm_seek / mmdm_set_history as after mmdm_begin. */
 int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, void* stream);
+/* mmdm_begin_ragged with the loop's other arguments: mmdm_begin_opts for a RAGGED batch (two-chain sampler; every precision mode; in2IN / InterGen
+ * denoisers and MDM as denoiser 1 where ragged batches cover it).  The rule of ragged batches holds with every option: each item is BIT-IDENTICAL to
+ * the same item sampled alone with the same options (tests/test_gpu_ragged_opts.py).  A zeroed struct (or opts == NULL) is mmdm_begin_ragged.  Device
+ * buffers are PACKED like x_T -- the items' frames back to back -- are the caller's and must stay alive until the stream has passed the call's last
+ * step; host arrays are consumed before the call returns, as the lengths are.
+ *   noise_source  0 = none; 1 = `noise` [noise_steps, sum(lens), 524]: slot k holds, item after item, what each item's own call would be handed
+ *                 as slot k; noise_steps >= S - skip_timesteps; 2 = generated on the device, keyed PER ITEM: item b draws element (t, column) of loop
+ *                 position k as mmdm_randn_f32(item_seed[b], k, item_noise_row[b] + 1, T_b) writes it at [item_noise_row[b], t, column] -- the noise of
+ *                 batch row item_noise_row[b] of a uniform call seeded item_seed[b] (the generator's counter holds neither B nor T).  item_seed: B HOST
+ *                 values, required for source 2; item_noise_row: B HOST ints, NULL = all zero (every item its own B = 1 call).
+ *   x_start       [sum(lens), 524]: each item's first lens[b] frames; columns 0, 2, 262, 264 of both chains' real rows are overwritten at every step.
+ *   init_image    [sum(lens), 524]; init_zeros, init_coef, skip_timesteps as in mmdm_begin_options.  eta and skip_timesteps belong to the CALL: one
+ *                 step index serves the batch.  Padding rows of the group stay zero and receive no noise.
+ * Everything that depends on the lengths or on an option's VALUE is device data (the slot stride of the noise buffer included): captured graphs are
+ * keyed by (noise_source, x_start given) beside the ragged key (B, rows, query tiles of the longest item, S) -- other values and other lengths of the
+ * same bucket replay the same graph, another form never does.  mmdm_run's check against the noise buffer and mmdm_seek behave as after mmdm_begin_opts.
+ * MMDM_ERR_STATE: eta table and noise source not both present / both absent.  MMDM_ERR_ARG: noise_steps < S - skip_timesteps, skip_timesteps outside
+ * [0, S), noise_source 2 without item_seed.  MMDM_ERR_UNSUPPORTED: single_only != 0 with any option set; a key mask on the handle. */
+typedef struct {
+    int noise_source;
+    int noise_steps;
+    const float* noise;
+    const unsigned long long* item_seed;
+    const int* item_noise_row;
+    const float* x_start;
+    const float* init_image;
+    int init_zeros;
+    float init_coef[2];
+    int skip_timesteps;
+} mmdm_begin_ragged_options;
+int mmdm_begin_ragged_opts(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, const mmdm_begin_ragged_options* opts, void* stream);
 /* Frame rows per half of the CFG-doubled batch in the begun call's buffers (uniform: B * T), the frames that are real (ragged: sum(lens)),
  * and whether the call is ragged.  Each pointer may be NULL. */
 int mmdm_call_rows(mmdm_handle h, int* rows, int* real_rows, int* ragged);

@@ -49,6 +49,12 @@ class BeginOptions(C.Structure):
                 ("skip_timesteps", C.c_int)]
 
 
+class BeginRaggedOptions(C.Structure):
+    """mmdm_begin_ragged_options (include/mmdm.h)."""
+    _fields_ = [("noise_source", C.c_int), ("noise_steps", C.c_int), ("noise", C.c_void_p), ("item_seed", C.c_void_p), ("item_noise_row", C.c_void_p),
+                ("x_start", C.c_void_p), ("init_image", C.c_void_p), ("init_zeros", C.c_int), ("init_coef", C.c_float * 2), ("skip_timesteps", C.c_int)]
+
+
 # every symbol include/mmdm.h declares: name -> (restype, argtypes)
 _I, _VP = C.c_int, C.c_void_p
 SYMBOLS = {
@@ -107,6 +113,7 @@ SYMBOLS = {
     "mmdm_begin_opts": (_I, [_VP, _VP, _VP, _I, _I, C.POINTER(BeginOptions), _VP]),
     "mmdm_randn_f32": (_I, [C.c_ulonglong, _I, _I, _I, _VP, _VP]),
     "mmdm_begin_ragged": (_I, [_VP, _VP, _VP, _I, _VP, _VP]),
+    "mmdm_begin_ragged_opts": (_I, [_VP, _VP, _VP, _I, _VP, C.POINTER(BeginRaggedOptions), _VP]),
     "mmdm_call_rows": (_I, [_VP, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "mmdm_attention_ragged_f32": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "mmdm_attention_ragged_opts_f32": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),

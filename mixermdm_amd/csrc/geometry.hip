@@ -326,12 +326,15 @@ __device__ __forceinline__ const NoiseArgs& noise_args(const NoiseArgs& a) { ret
 // NOISE: 0 = the deterministic update (eta = 0; no extra argument: NA is empty and the kernel is what it was before the forms 1 / 2 existed),
 // 1 = + sigma * noise[loop_pos] from the caller's buffer [n_steps, B, T, 524], 2 = + sigma * step_normal(seed, loop_pos, ...).  Forms 1 / 2 read
 // sqrt(1 - ab_prev - sigma^2) and sigma from the eta table and add no noise at i = 0 (gaussian_diffusion.py:1958-1963); the same noise goes to both chains.
+// RAG forms 1 / 2: the buffer is packed [n_steps, sum(lens), 524] -- a slot's element is the chains' own index, the slot stride comes from the descriptor
+// (it differs between batches that replay one graph) -- and the generator is keyed per item: (item_seed[b], item_noise_row[b]) stand for (seed, b), so that
+// an item draws what it draws in the call it is meant to equal.  Padding rows have left by then.
 template <bool RAG, int NOISE = 0, typename... NA>
 __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restrict__ m, const float* __restrict__ stats, const float* __restrict__ coef,
                                                            int S, const int* __restrict__ step_idx, float* __restrict__ x, float* __restrict__ x2,
                                                            float* __restrict__ px1, float* __restrict__ px2, const float* __restrict__ floor_ws,
                                                            int B, int T, int align, mmdm_rag rg, NA... na) {
-    static_assert(NOISE == 0 ? sizeof...(NA) == 0 : (sizeof...(NA) == 1 && !RAG), "forms 1 / 2 take one NoiseArgs and are uniform-batch only");
+    static_assert(NOISE == 0 ? sizeof...(NA) == 0 : sizeof...(NA) == 1, "forms 1 / 2 take one NoiseArgs");
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     int j, t, p, b;
     size_t seq;
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restric
     const int i = *step_idx;
     const float c0 = coef[i], c1 = coef[S + i], c2 = coef[2 * S + i];
     float c3, sigma = 0.f;
-    int lp = 0;
+    int lp = 0, nb = b;                          // nb: the item's `b` in the generator's counter
     unsigned long long seed = 0;
     const float* nz = nullptr;
     if constexpr (NOISE == 0) c3 = coef[3 * S + i];
@@ -365,7 +368,9 @@ __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restric
         c3 = a.coef_eta[i];
         sigma = a.coef_eta[S + i];
         lp = *a.loop_pos;
-        if constexpr (NOISE == 1) nz = lp < a.od->noise_steps ? a.od->noise + (size_t)lp * B * T * NF2 : nullptr;   // (the host refuses a run past the buffer)
+        if constexpr (NOISE == 1 && RAG) nz = lp < a.od->noise_steps ? a.od->noise + (size_t)lp * (size_t)a.od->noise_stride : nullptr;
+        else if constexpr (NOISE == 1) nz = lp < a.od->noise_steps ? a.od->noise + (size_t)lp * B * T * NF2 : nullptr;   // (the host refuses a run past the buffer)
+        else if constexpr (RAG) { seed = a.od->item_seed[b]; nb = a.od->item_noise_row[b]; }
         else seed = a.od->seed;
     }
     const bool norm = i > 0;                                     // `if t[0] > 0`  gaussian_diffusion.py:2052
@@ -442,7 +447,7 @@ __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restric
             if (i != 0) {                                        // nonzero_mask * sigma * noise, one draw for both chains   :1947, 1958-1963
                 float z;
                 if constexpr (NOISE == 1) z = nz ? nz[e] : 0.f;
-                else z = step_normal(seed, lp, b, t, p * NF + c);
+                else z = step_normal(seed, lp, nb, t, p * NF + c);
                 const float sn = sigma * z;
                 va += sn; vb += sn;
             }
@@ -511,6 +516,20 @@ __global__ __launch_bounds__(256) void pin_root_kernel(float* __restrict__ x, fl
     x2[e] = v;
 }
 
+// ragged form: one thread per (frame row of the group, pinned column); x_start is packed [sum(lens), 524] like x_T, padding rows are never looked up
+__global__ __launch_bounds__(256) void pin_root_rag_kernel(float* __restrict__ x, float* __restrict__ x2, const mmdm_opts_desc* __restrict__ od, mmdm_rag rg) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rg.rows * 4) return;
+    const float* xs = od->x_start;
+    if (!xs) return;
+    const int k = idx & 3, r = idx >> 2;
+    if (rg.row_item[r] < 0) return;
+    const size_t e = (size_t)r * NF2 + (k >> 1) * NF + (k & 1) * 2;
+    const float v = xs[e];
+    x[e] = v;
+    x2[e] = v;
+}
+
 // q_sample at the start of a call (gaussian_diffusion.py:1859-1863, 465-485): x = a * init + b * x_T on both chains (init == nullptr: zeros)
 __global__ __launch_bounds__(256) void q_sample_kernel(float* __restrict__ x, float* __restrict__ x2, const float* __restrict__ init, float a, float b, size_t total) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -521,6 +540,14 @@ __global__ __launch_bounds__(256) void q_sample_kernel(float* __restrict__ x, fl
 }
 
 __global__ void set_opts_kernel(mmdm_opts_desc* d, mmdm_opts_desc v) { *d = v; }
+
+struct RagItemNoise { unsigned long long seed[MMDM_RAG_MAX_ITEMS]; int row[MMDM_RAG_MAX_ITEMS]; };
+__global__ __launch_bounds__(256) void set_item_noise_kernel(RagItemNoise v, int B, unsigned long long* __restrict__ item_seed, int* __restrict__ item_noise_row) {
+    const int b = threadIdx.x;
+    if (b >= B) return;
+    item_seed[b] = v.seed[b];
+    item_noise_row[b] = v.row[b];
+}
 
 // which: 0 -> hd->o1, 1 -> hd->o2; a null destination (history not requested for this call) makes the launch a no-op
 __global__ void hist_copy_kernel(const float* __restrict__ src, const mmdm_hist_desc* __restrict__ hd, int which, size_t count, const int* __restrict__ loop_pos) {
@@ -761,6 +788,20 @@ int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, int B, int T, h
     return mmdm_check_launch("pin_root");
 }
 
+int mmdm_pin_root_rag(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rag& rg, hipStream_t st) {
+    hipLaunchKernelGGL(pin_root_rag_kernel, dim3((rg.rows * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, rg);
+    return mmdm_check_launch("pin_root_rag");
+}
+
+int mmdm_set_item_noise(const unsigned long long* seed_host, const int* row_host, int B, unsigned long long* item_seed, int* item_noise_row, hipStream_t st) {
+    if (B <= 0 || B > MMDM_RAG_MAX_ITEMS || !seed_host) return mmdm_set_error(MMDM_ERR_ARG, "ragged batch: per-item seeds of %d items (1 .. %d)", B, MMDM_RAG_MAX_ITEMS);
+    static_assert(MMDM_RAG_MAX_ITEMS <= 256, "one block of 256 threads writes the items");
+    RagItemNoise v;
+    for (int b = 0; b < MMDM_RAG_MAX_ITEMS; ++b) { v.seed[b] = b < B ? seed_host[b] : 0ull; v.row[b] = (b < B && row_host) ? row_host[b] : 0; }
+    hipLaunchKernelGGL(set_item_noise_kernel, dim3(1), dim3(256), 0, st, v, B, item_seed, item_noise_row);
+    return mmdm_check_launch("set_item_noise");
+}
+
 int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st) {
     hipLaunchKernelGGL(q_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, x2, init, a, b, total);
     return mmdm_check_launch("q_sample");
@@ -790,6 +831,26 @@ int mmdm_xstart_ddim_rag(const float* model_out, const float* stats, const float
     hipLaunchKernelGGL(xstart_ddim_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
                        pred_xstart, pred_xstart2, floor_ws, rg.B, 0, align, rg);
     return mmdm_check_launch("xstart_ddim_rag");
+}
+
+// the ragged update with step noise (form 1: the packed buffer, 2: the generator keyed per item)
+int mmdm_xstart_ddim_noise_rag(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
+                               const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
+                               int align, const mmdm_rag& rg, hipStream_t st) {
+    if (form != 1 && form != 2) return mmdm_set_error(MMDM_ERR_ARG, "xstart_ddim_noise_rag: form %d", form);
+    if (align) {
+        hipLaunchKernelGGL(floor_kernel<true>, dim3(rg.B * 2), dim3(256), 0, st, model_out, floor_ws, 0, rg);
+        if (int rc = mmdm_check_launch("floor_rag")) return rc;
+    }
+    const int total = rg.rows * 2 * MMDM_NJ;
+    const NoiseArgs na{coef_eta, od, loop_pos};
+    if (form == 1)
+        hipLaunchKernelGGL((xstart_ddim_kernel<true, 1, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
+                           pred_xstart, pred_xstart2, floor_ws, rg.B, 0, align, rg, na);
+    else
+        hipLaunchKernelGGL((xstart_ddim_kernel<true, 2, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
+                           pred_xstart, pred_xstart2, floor_ws, rg.B, 0, align, rg, na);
+    return mmdm_check_launch("xstart_ddim_noise_rag");
 }
 
 extern "C" int mmdm_cfg_ddim_f32(const float* m, const float* coef, int S, const int* step_idx, float cfg_scale,

@@ -105,6 +105,11 @@ struct mmdm_opts_desc {
     const float* x_start;             // [B, xs_T, 524]; null = not pinned
     unsigned long long seed;          // device generator (noise form 2)
     int noise_steps, xs_T;
+    // ragged calls (mmdm_begin_ragged_opts): noise [noise_steps, sum(lens), 524] and x_start [sum(lens), 524] are PACKED like x_T; what depends on the
+    // batch's lengths or items is device data too -- a captured ragged graph serves every batch of its row bucket
+    long long noise_stride;           // elements between two slots of the packed noise buffer: sum(lens) * 524
+    const unsigned long long* item_seed;     // [B] generator seed of every item (noise form 2); the handle's own array
+    const int* item_noise_row;        // [B] the `b` of every item in the generator's counter; the handle's own array
 };
 int mmdm_set_opts_desc(mmdm_opts_desc* d, const mmdm_opts_desc& v, hipStream_t st);
 int mmdm_xstart_ddim_noise(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
@@ -131,6 +136,13 @@ int mmdm_blend_cfg_rag(const float* out1, const float* out2, const float* w, int
                        float* model_out, const mmdm_hist_desc* hd, const int* loop_pos, const mmdm_rag& rg, hipStream_t st);
 int mmdm_xstart_ddim_rag(const float* model_out, const float* stats, const float* coef, int S, const int* step_idx,
                          float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws, int align, const mmdm_rag& rg, hipStream_t st);
+// the ragged update with step noise (form 1: the packed buffer, 2: the generator keyed per item) and the ragged root pin (geometry.hip)
+int mmdm_xstart_ddim_noise_rag(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
+                               const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
+                               int align, const mmdm_rag& rg, hipStream_t st);
+int mmdm_pin_root_rag(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rag& rg, hipStream_t st);
+// per-item generator identity of a ragged call: B host values each, passed by value like the lengths (row_host may be null: zeros)
+int mmdm_set_item_noise(const unsigned long long* seed_host, const int* row_host, int B, unsigned long long* item_seed, int* item_noise_row, hipStream_t st);
 int mmdm_linear_f32_ex(const float* A, int lda, const float* W, int ldw, int Kw, const float* bias, float* C, int ldc,
                        int M, int N, int K, int epilogue, const float* extra, int ld_extra, int period, void* stream);
 int mmdm_mdm_pack(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,

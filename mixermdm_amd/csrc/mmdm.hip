@@ -286,6 +286,9 @@ struct mmdm_handle_s {
     // options of the begun call (mmdm_begin_opts): host mirror + the device-side descriptor the step's kernels read (kernels.h: mmdm_opts_desc)
     mmdm_opts_desc opts = {nullptr, nullptr, 0ull, 0, 0};
     mmdm_opts_desc* d_opts = nullptr;
+    // ragged calls with the device generator (mmdm_begin_ragged_opts): every item's seed and its `b` in the generator's counter, [MMDM_RAG_MAX_ITEMS] each
+    unsigned long long* d_item_seed = nullptr;
+    int* d_item_noise_row = nullptr;
     int noise_form = 0;                                    // 0 = none, 1 = the caller's buffer, 2 = the device generator: which update kernel a step launches
     bool pinned = false;                                   // x_start given: pin_root_kernel is the first node of a step
     int host_loop = 0;                                     // mirror of loop_pos
@@ -1047,7 +1050,7 @@ int run_step(const Ctx& c) {
     }
     const bool dual = H->cfg.single_only == 3;
     // x_start of the call (mmdm_begin_opts): both chains' root ground paths are overwritten before the models run -- the first node of the step
-    if (H->pinned) RC(mmdm_pin_root(H->x, H->x2, H->d_opts, B, T, c.st));
+    if (H->pinned) RC(c.rag() ? mmdm_pin_root_rag(H->x, H->x2, H->d_opts, c.g->rg, c.st) : mmdm_pin_root(H->x, H->x2, H->d_opts, B, T, c.st));
     // the individual model on both persons: in2IN blocks, the "dual_individual" variant of them, or MDMDenoiser
     auto model1 = [&](const Ctx& cc) -> int {
         if (H->d1.kind == 1) return run_denoiser_mdm(cc, H->d1, H->x, B, 2, NF2, n, T, H->cond_cat + 3 * H->cfg.text_dim, H->cond_w, H->o1, NF2);
@@ -1081,8 +1084,10 @@ int run_step(const Ctx& c) {
         return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
     }
     RC(mixer_core(c, B, T));
-    if (c.rag()) RC(mmdm_xstart_ddim_rag(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
-                                         H->cfg.xstart_align, c.g->rg, c.st));
+    if (c.rag() && H->noise_form) RC(mmdm_xstart_ddim_noise_rag(H->noise_form, H->model_out, H->d_stats, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts,
+                                                                H->x, H->x2, H->px1, H->px2, H->floor_ws, H->cfg.xstart_align, c.g->rg, c.st));
+    else if (c.rag()) RC(mmdm_xstart_ddim_rag(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
+                                              H->cfg.xstart_align, c.g->rg, c.st));
     else if (H->noise_form) RC(mmdm_xstart_ddim_noise(H->noise_form, H->model_out, H->d_stats, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts,
                                                       H->x, H->x2, H->px1, H->px2, H->floor_ws, B, T, H->cfg.xstart_align, c.st));
     else RC(mmdm_xstart_ddim_f32(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
@@ -1353,6 +1358,11 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
             h->d_tok_item_off = h->d_tok; h->d_tok_item_len = h->d_tok_item_off + nb; h->d_tok_row_item = h->d_tok_item_len + nb;
             h->d_tok_row_pos = h->d_tok_row_item + tcap; h->d_tok_seq_off = h->d_tok_row_pos + tcap; h->d_tok_seq_len = h->d_tok_seq_off + G * nb;
         }
+        if (so == 0) {      // per-item generator identity (8-byte seeds first: the allocation's own alignment serves them)
+            if ((rc = dalloc(h, &tmp, 3 * (size_t)MMDM_RAG_MAX_ITEMS))) return fail(rc);
+            h->d_item_seed = reinterpret_cast<unsigned long long*>(tmp);
+            h->d_item_noise_row = reinterpret_cast<int*>(h->d_item_seed + MMDM_RAG_MAX_ITEMS);
+        }
         if (const char* e = getenv("MMDM_RAG_BUCKET")) { long v = atol(e); if (v >= 1 && v <= 4096) h->rag_bucket = (int)v; }
     }
     *out = h;
@@ -1594,20 +1604,24 @@ extern "C" int mmdm_set_eta(mmdm_handle h, const float* coef_eta_host, int S) {
 }
 
 // mmdm_begin (lens == nullptr: B items of T frames; o: the call's options or nullptr) and mmdm_begin_ragged (lens = B host ints, x_T = the items'
-// frames back to back)
+// frames back to back).  ro: the call came through mmdm_begin_ragged_opts -- `o` then holds its options with the buffers PACKED like x_T, and ro's per-item
+// host arrays stand for `seed`
+struct RagItemOpts { const unsigned long long* seed; const int* row; };
 static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B, int T, const int* lens, void* stream, const mmdm_begin_options* o = nullptr,
-                      const char* who = "mmdm_begin") {
+                      const char* who = "mmdm_begin", const RagItemOpts* ro = nullptr) {
     if (!h || !cond || !x_T) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_begin: null argument");
     if (!h->prepared || h->S == 0) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_begin: prepare() and set_schedule() first"));
     static const mmdm_begin_options none = {};
     if (!o) o = &none;
     const bool any = o->noise_source || o->noise || o->x_start || o->init_image || o->init_zeros || o->skip_timesteps;
-    if (lens && h->eta_set)
-        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: eta is set on the handle; the stochastic update covers uniform batches (clear it with mmdm_set_eta(h, NULL, 0))"));
+    if (lens && h->eta_set && !ro)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: eta is set on the handle; the stochastic update covers uniform batches and ragged calls that name a noise source (mmdm_begin_ragged_opts); or clear it with mmdm_set_eta(h, NULL, 0)"));
     if (any && h->cfg.single_only != 0)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: step noise, x_start, init_image and skip_timesteps cover the two-chain MixerMDM sampler (single_only = %d)", who, h->cfg.single_only));
     if (o->noise_source < 0 || o->noise_source > 2 || (o->noise_source == 1 && !o->noise))
         return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: noise_source must be 0 (none), 1 (buffer, not NULL) or 2 (seed)", who));
+    if (ro && o->noise_source == 2 && !ro->seed)
+        return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: noise_source 2 needs item_seed (one seed per item)", who));
     if (o->skip_timesteps < 0 || o->skip_timesteps >= h->S)
         return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: skip_timesteps=%d outside [0, %d)", who, o->skip_timesteps, h->S));
     if (h->eta_set && !o->noise_source)
@@ -1616,7 +1630,7 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
         return herr(h, mmdm_set_error(MMDM_ERR_STATE, "%s: a noise source is given and no eta table is set (mmdm_set_eta after mmdm_set_schedule)", who));
     if (o->noise_source == 1 && o->noise_steps < h->S - o->skip_timesteps)
         return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: the noise buffer holds %d steps, %d are left in the schedule", who, o->noise_steps, h->S - o->skip_timesteps));
-    if (o->x_start && o->x_start_frames < T)
+    if (!lens && o->x_start && o->x_start_frames < T)
         return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: x_start has %d frames, the call has T=%d", who, o->x_start_frames, T));
     Geom g;
     if (lens && h->mask_rows)
@@ -1720,9 +1734,12 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     // Caller pointers and the seed go to the device-side descriptor ON THE STREAM, behind any step of the previous call still in flight
     const int i0 = h->S - 1 - o->skip_timesteps;           // first executed step: indices = range(S - skip)[::-1]   gaussian_diffusion.py:1857
     if (o->init_image || o->init_zeros || o->skip_timesteps)      // q_sample(init_image, i0, x_T), img2 = img.clone()   :1854-1863 (skip and no image: zeros)
-        RC(herr(h, mmdm_q_sample(h->x, h->x2, o->init_image, o->init_coef[0], o->init_coef[1], (size_t)B * T * NF2, st)));
-    h->opts = mmdm_opts_desc{o->noise_source == 1 ? o->noise : nullptr, o->x_start, o->noise_source == 2 ? o->seed : 0ull,
-                             o->noise_source == 1 ? o->noise_steps : 0, o->x_start ? o->x_start_frames : 0};
+        // (ragged: the group's first sum(lens) rows -- the image is packed like x_T and never indexed for a padding row, which stays zero)
+        RC(herr(h, mmdm_q_sample(h->x, h->x2, o->init_image, o->init_coef[0], o->init_coef[1], (size_t)g.real_rows * NF2, st)));
+    if (g.rag && o->noise_source == 2) RC(herr(h, mmdm_set_item_noise(ro->seed, ro->row, B, h->d_item_seed, h->d_item_noise_row, st)));
+    h->opts = mmdm_opts_desc{o->noise_source == 1 ? o->noise : nullptr, o->x_start, (o->noise_source == 2 && !g.rag) ? o->seed : 0ull,
+                             o->noise_source == 1 ? o->noise_steps : 0, (o->x_start && !g.rag) ? o->x_start_frames : 0,
+                             g.rag ? (long long)g.real_rows * NF2 : 0ll, g.rag ? h->d_item_seed : nullptr, g.rag ? h->d_item_noise_row : nullptr};
     RC(herr(h, mmdm_set_opts_desc(h->d_opts, h->opts, st)));
     h->noise_form = o->noise_source;
     h->pinned = o->x_start != nullptr;
@@ -1749,6 +1766,21 @@ extern "C" int mmdm_begin_opts(mmdm_handle h, const float* cond, const float* x_
 extern "C" int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, void* stream) {
     if (!lens_host) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_begin_ragged: null lengths");
     return begin_impl(h, cond, x_T, B, 0, lens_host, stream);
+}
+
+extern "C" int mmdm_begin_ragged_opts(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, const mmdm_begin_ragged_options* opts,
+                                      void* stream) {
+    if (!lens_host) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_begin_ragged_opts: null lengths");
+    static const mmdm_begin_ragged_options none = {};
+    const mmdm_begin_ragged_options* r = opts ? opts : &none;
+    if (!(r->noise_source || r->noise || r->item_seed || r->item_noise_row || r->x_start || r->init_image || r->init_zeros || r->skip_timesteps) && !(h && h->eta_set))
+        return begin_impl(h, cond, x_T, B, 0, lens_host, stream);          // a zeroed struct is mmdm_begin_ragged
+    mmdm_begin_options o = {};
+    o.noise_source = r->noise_source; o.noise_steps = r->noise_steps; o.noise = r->noise;
+    o.x_start = r->x_start; o.init_zeros = r->init_zeros; o.init_image = r->init_image;
+    o.init_coef[0] = r->init_coef[0]; o.init_coef[1] = r->init_coef[1]; o.skip_timesteps = r->skip_timesteps;
+    const RagItemOpts ro{r->item_seed, r->item_noise_row};
+    return begin_impl(h, cond, x_T, B, 0, lens_host, stream, &o, "mmdm_begin_ragged_opts", &ro);
 }
 
 extern "C" int mmdm_call_rows(mmdm_handle h, int* rows, int* real_rows, int* ragged) {

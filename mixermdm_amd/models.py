@@ -466,7 +466,8 @@ class MixerMDM(nn.Module):
             pool["kids"].append(main.share(max_batch=B, max_frames=max(T, self.num_frames)))
         return [main] + pool["kids"][:k - 1]
 
-    def sample_many(self, batches, mode="eval_intermediate", batching="ragged", inflight=2, max_rows=4800, max_items=64, keep_history=None):
+    def sample_many(self, batches, mode="eval_intermediate", batching="ragged", inflight=2, max_rows=4800, max_items=64, keep_history=None, *,
+                    eta=0.0, skip_timesteps=0):
         """Many sampling calls in one go -- what the reference's callers do one after the other: the inference script calls ``model(batch)`` ten
         times at B = 1 (src/scripts/infer/mixermdm.py:184-188), the evaluation datasets call ``forward_test`` once per item with that item's
         own length (src/evaluation/datasets.py:100-116).  `batches`: reference-style batch dicts (text lists or a precomputed 'cond' [b, 8*768];
@@ -479,9 +480,38 @@ class MixerMDM(nn.Module):
                                  kept for callers whose requests arrive at different times, not as a throughput lever;
                   "ragged"     = the calls' motions packed into ragged batches of <= max_rows frames / <= max_items motions
                                  (mmdm_begin_ragged: per-sequence lengths as device data; GEMMs at the efficiency of a full batch).
-        keep_history: None = what the mode says (store_influence -> influence lists; "eval" -> out1 / out2 / out_influenced), False = outputs only."""
+        keep_history: None = what the mode says (store_influence -> influence lists; "eval" -> out1 / out2 / out_influenced), False = outputs only.
+
+        The loop's other arguments (ddim_sample_loop's; "sequential" and "ragged", bitwise the same motions and histories either way): eta and
+        skip_timesteps belong to the call; a batch dict may carry 'seed' (int) or 'step_noise' [>= S - skip, b, T, 524] (read at eta > 0 only; with
+        neither, one seed per batch is drawn from torch's default generator, in batch order), 'x_start' [b, T' >= T, 524] and 'init_image' [b, T, 524].
+        Motion j of a batch draws the noise of row j of that batch's call.  One noise form per call, and x_start / init_image for every batch or
+        none (a step's kernel form belongs to the call): otherwise ValueError.  Histories hold S - skip_timesteps entries."""
         if batching not in ("sequential", "inflight", "ragged"):
             raise ValueError(f"batching {batching!r} not recognized")
+        eta, skip = float(eta), int(skip_timesteps)
+        if eta < 0:
+            raise ValueError(f"eta={eta} must be >= 0")
+        has = lambda k: [b.get(k) is not None for b in batches]
+        for k in ("x_start", "init_image"):
+            if any(has(k)) and not all(has(k)):
+                raise ValueError(f"sample_many: batch {has(k).index(not has(k)[0])} differs from batch 0 in whether it gives {k!r}: give it for every batch or for none")
+        use_opts = bool(eta or skip or any(has("x_start")) or any(has("init_image")))
+        if use_opts and batching == "inflight":
+            raise ValueError('sample_many: batching="inflight" takes no eta / skip_timesteps / x_start / init_image; use "ragged" or "sequential"')
+        form = None                                       # "seed" | "noise" at eta > 0
+        seeds = [None] * len(batches)
+        if eta:
+            for i, b in enumerate(batches):
+                sd, sn = b.get("seed"), b.get("step_noise")
+                if sd is not None and sn is not None:
+                    raise ValueError(f"sample_many: batch {i} gives both 'seed' and 'step_noise'")
+                f = "noise" if sn is not None else "seed"
+                if form is not None and f != form:
+                    raise ValueError(f"sample_many: batch {i} names its step noise as a {f!r}, batch 0 as a {form!r}: one noise form per call")
+                form = f
+                if f == "seed":                           # as ddim_sample_loop: an un-named seed comes from torch's default generator
+                    seeds[i] = int(sd) if sd is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
         m = self.mixing
         m.mode = mode
         names = []
@@ -497,7 +527,9 @@ class MixerMDM(nn.Module):
         dev = self.device
         xs = [b["x_T"].to(dev, torch.float32) if "x_T" in b else torch.randn(nb, T, self.nfeats * 2, device=dev) for b, nb, T in zip(batches, Bs, Ts)]
         sch = MixerDiffusion(use_timesteps=space_timesteps(self.diffusion_steps, self.sampling_strategy), betas=self.betas).schedule
-        slots = (sch.num_timesteps + self.history_every - 1) // self.history_every
+        if not 0 <= skip < sch.num_timesteps:
+            raise ValueError(f"skip_timesteps={skip} outside [0, {sch.num_timesteps})")
+        slots = (sch.num_timesteps - skip + self.history_every - 1) // self.history_every      # one entry per EXECUTED step
         keys = ("influence_i1", "influence_i2") + (("out1", "out2", "out_influenced") if mode == "eval" else ())
         results = [{"output": None, **{k: [] for k in keys}} for _ in batches]
         if batching == "sequential":
@@ -508,7 +540,14 @@ class MixerMDM(nn.Module):
                 if not names:
                     m.store_influence = False
                 try:
-                    results[i] = self.forward(bb) if mode == "eval" else self.forward_test(bb)
+                    if use_opts:                          # the uniform option path (ddim_sample_loop -> mmdm_begin_opts)
+                        out = self._sample(bb, mode, eta=eta, skip_timesteps=skip, seed=seeds[i], step_noise=b.get("step_noise") if form == "noise" else None,
+                                           x_start=b.get("x_start"), init_image=b.get("init_image"))
+                        results[i] = {"output": out, "influence_i1": m.history_influence_i1, "influence_i2": m.history_influence_i2}
+                        if mode == "eval":
+                            results[i].update(out1=m.history_out1, out2=m.history_out2, out_influenced=m.history_out_influenced)
+                    else:
+                        results[i] = self.forward(bb) if mode == "eval" else self.forward_test(bb)
                 finally:
                     m.store_influence = keep
             return results
@@ -569,16 +608,42 @@ class MixerMDM(nn.Module):
         outs = [[None] * nb for nb in Bs]
         hists = [[None] * nb for nb in Bs]
         pend = []
-        for g in groups:
-            lens = [Ts[i] for i, _ in g]
-            need = slots * 2 * (sum(lens) + 128) * 4 * sum(wi if n.startswith("influence") else 524 for n in names)
-            if need > HISTORY_BUDGET_BYTES:
-                raise MemoryError(f"history side outputs of a ragged batch of {sum(lens)} frames need {need / 2**30:.1f} GiB; lower max_rows, set "
-                                  "model.history_every, or pass keep_history=False")
-            cond_g = torch.cat([conds[i][j:j + 1] for i, j in g], 0)
-            x_g = [xs[i][j] for i, j in g]
-            items, hist, ev = smp.sample_ragged_async(cond_g, x_g, lens, history=names or None, history_every=self.history_every)
-            pend.append((g, items, hist, ev, smp.item_slices(), smp.rows))
+        steps = sch.num_timesteps - skip
+        if form == "noise":
+            for i, b in enumerate(batches):
+                sn = b["step_noise"]
+                if sn.dim() != 4 or sn.shape[0] < steps or tuple(sn.shape[1:]) != (Bs[i], Ts[i], 524):
+                    raise ValueError(f"sample_many: batch {i}: step_noise [>= {steps}, {Bs[i]}, {Ts[i]}, 524] expected, got {tuple(sn.shape)}")
+        for k in ("x_start", "init_image"):
+            for i, b in enumerate(batches):
+                if b.get(k) is not None and (b[k].dim() != 3 or b[k].shape[0] != Bs[i]):
+                    raise ValueError(f"sample_many: batch {i}: {k} [{Bs[i]}, T, 524] expected, got {tuple(b[k].shape)}")
+        if eta:
+            smp.set_eta(eta)
+        try:
+            for g in groups:
+                lens = [Ts[i] for i, _ in g]
+                need = slots * 2 * (sum(lens) + 128) * 4 * sum(wi if n.startswith("influence") else 524 for n in names)
+                if need > HISTORY_BUDGET_BYTES:
+                    raise MemoryError(f"history side outputs of a ragged batch of {sum(lens)} frames need {need / 2**30:.1f} GiB; lower max_rows, set "
+                                      "model.history_every, or pass keep_history=False")
+                cond_g = torch.cat([conds[i][j:j + 1] for i, j in g], 0)
+                x_g = [xs[i][j] for i, j in g]
+                kw = {}
+                if use_opts:                              # motion j of batch i: (seed_i, noise row j), or its slice of the batch's buffers
+                    kw["skip_timesteps"] = skip
+                    if form == "seed":
+                        kw["seeds"], kw["noise_rows"] = [seeds[i] for i, _ in g], [j for _, j in g]
+                    elif form == "noise":
+                        kw["noise"] = [batches[i]["step_noise"][:steps, j] for i, j in g]
+                    for k in ("x_start", "init_image"):
+                        if batches[g[0][0]].get(k) is not None:
+                            kw[k] = [batches[i][k][j] for i, j in g]
+                items, hist, ev = smp.sample_ragged_async(cond_g, x_g, lens, history=names or None, history_every=self.history_every, **kw)
+                pend.append((g, items, hist, ev, smp.item_slices(), smp.rows))
+        finally:
+            if eta:                                       # eta belongs to this call: the handle is left at eta = 0, as _run_loop_on leaves it
+                smp.set_eta(0.0)
         for g, items, hist, ev, slices, rows in pend:
             ev.synchronize()
             for (i, j), it, (o, t) in zip(g, items, slices):
@@ -596,7 +661,8 @@ class MixerMDM(nn.Module):
                     results[i][k] = list(torch.cat([cond_rows, unc_rows], 1).unbind(0))     # [2b, T, C] per kept step
         return results
 
-    def _sample(self, batch, mode):
+    def _sample(self, batch, mode, **loop_kw):
+        """loop_kw: ddim_sample_loop's other arguments (eta, skip_timesteps, init_image, x_start, step_noise, seed); none for forward / forward_test."""
         self.mixing.mode = mode
         cond = self.generate_cond(batch)
         B = cond.shape[0]
@@ -604,7 +670,7 @@ class MixerMDM(nn.Module):
         self.diffusion_test = MixerDiffusion(use_timesteps=space_timesteps(self.diffusion_steps, self.sampling_strategy), betas=self.betas)
         self.cfg_model = ClassifierFreeSampleModelX2(self.mixing, self.cfg_mixing_weight)
         return self.diffusion_test.ddim_sample_loop(self.cfg_model, (B, T, self.nfeats * 2), noise=batch.get("x_T"), clip_denoised=False,
-                                                    progress=True, model_kwargs={"mask": None, "cond": cond}, x_start=None)
+                                                    progress=True, model_kwargs={"mask": None, "cond": cond}, **{"x_start": None, **loop_kw})
 
     def forward(self, batch):
         """mixermdm.py:490-548."""

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Config, BeginOptions, load_library, check
+from ._lib import Config, BeginOptions, BeginRaggedOptions, load_library, check
 from .schedule import make_schedule
 
 STATS_ORDER = ("mean_hml", "std_hml", "mean_ih", "std_ih")
@@ -22,6 +22,81 @@ def pe_table(d_model, max_len=5000):
     pe[:, 0::2] = torch.sin(position * div_term)
     pe[:, 1::2] = torch.cos(position * div_term)
     return pe
+
+
+def pack_ragged_options(lens, *, noise=None, seeds=None, noise_rows=None, x_start=None, init_image=None, skip_timesteps=0):
+    """The options of a ragged call (Sampler.begin_ragged) as mmdm_begin_ragged_opts takes them -- buffers PACKED like x_T, the items' frames back
+    to back -- from packed tensors or per-item lists; needs no device (tensors stay where they are).  -> dict(noise [n, sum(lens), 524] | None,
+    seeds [B ints] | None, noise_rows [B ints] | None, x_start [sum(lens), 524] | None, init_image [sum(lens), 524] | None, skip_timesteps).
+      noise       [n, sum(lens), 524], or B tensors [n, T_i, 524] (one n)
+      seeds       B ints: every item its own call (noise_rows default to zeros); ONE int: the batch is one call (noise_rows default to range(B))
+      noise_rows  B ints >= 0: the `b` of every item in the generator's counter; overrides the defaults; needs seeds
+      x_start     [sum(lens), 524], or B tensors [T_i' >= T_i, 524], cut to T_i
+      init_image  [sum(lens), 524], or B tensors [T_i, 524]
+    Anything else is a ValueError."""
+    lens = [int(v) for v in lens]
+    B, total = len(lens), sum(lens)
+    if B == 0 or min(lens) <= 0:
+        raise ValueError(f"ragged options: lens {lens} (B >= 1 items of >= 1 frames)")
+    f32 = lambda t: torch.as_tensor(t).to(torch.float32)
+
+    def per_item(name, v):
+        if len(v) != B:
+            raise ValueError(f"ragged options: {name} lists {len(v)} items, the batch has {B}")
+        return [f32(t) for t in v]
+
+    if noise is not None and seeds is not None:
+        raise ValueError("ragged options: give the step noise as a buffer (noise=) or as seeds (seeds=), not both")
+    if noise_rows is not None and seeds is None:
+        raise ValueError("ragged options: noise_rows count the generator's batch rows and need seeds=")
+    if noise is not None:
+        if isinstance(noise, (list, tuple)):
+            parts = per_item("noise", noise)
+            for b, t in enumerate(parts):
+                if t.dim() != 3 or t.shape[0] != parts[0].shape[0] or tuple(t.shape[1:]) != (lens[b], 524):
+                    raise ValueError(f"ragged options: noise of item {b}: [n, {lens[b]}, 524] with one n for all items expected, got {tuple(t.shape)}")
+            noise = torch.cat(parts, 1)
+        else:
+            noise = f32(noise)
+        if noise.dim() != 3 or tuple(noise.shape[1:]) != (total, 524):
+            raise ValueError(f"ragged options: noise [steps, {total}, 524] expected, got {tuple(noise.shape)}")
+        noise = noise.contiguous()
+    if seeds is not None:
+        if isinstance(seeds, (int, np.integer)):
+            seeds, default_rows = [int(seeds)] * B, list(range(B))
+        else:
+            seeds, default_rows = [int(v) for v in seeds], [0] * B
+            if len(seeds) != B:
+                raise ValueError(f"ragged options: {len(seeds)} seeds for {B} items")
+        seeds = [v & 0xFFFFFFFFFFFFFFFF for v in seeds]
+        noise_rows = default_rows if noise_rows is None else [int(v) for v in noise_rows]
+        if len(noise_rows) != B or min(noise_rows) < 0:
+            raise ValueError(f"ragged options: noise_rows {noise_rows}: {B} ints >= 0 expected")
+    if x_start is not None:
+        if isinstance(x_start, (list, tuple)):
+            parts = per_item("x_start", x_start)
+            for b, t in enumerate(parts):
+                if t.dim() != 2 or t.shape[0] < lens[b] or t.shape[1] != 524:
+                    raise ValueError(f"ragged options: x_start of item {b}: [T' >= {lens[b]}, 524] expected, got {tuple(t.shape)}")
+            x_start = torch.cat([t[:n] for t, n in zip(parts, lens)], 0)
+        else:
+            x_start = f32(x_start)
+        if tuple(x_start.shape) != (total, 524):
+            raise ValueError(f"ragged options: x_start [{total}, 524] expected, got {tuple(x_start.shape)}")
+        x_start = x_start.contiguous()
+    if init_image is not None:
+        if isinstance(init_image, (list, tuple)):
+            parts = per_item("init_image", init_image)
+            for b, t in enumerate(parts):
+                if tuple(t.shape) != (lens[b], 524):
+                    raise ValueError(f"ragged options: init_image of item {b}: [{lens[b]}, 524] expected, got {tuple(t.shape)}")
+            init_image = torch.cat(parts, 0)
+        else:
+            init_image = f32(init_image)
+        if tuple(init_image.shape) != (total, 524):
+            raise ValueError(f"ragged options: init_image [{total}, 524] expected, got {tuple(init_image.shape)}")
+        init_image = init_image.contiguous()
+    return dict(noise=noise, seeds=seeds, noise_rows=noise_rows, x_start=x_start, init_image=init_image, skip_timesteps=int(skip_timesteps))
 
 
 class Sampler:
@@ -253,10 +328,16 @@ class Sampler:
         self._steps = S - skip
         return self
 
-    def begin_ragged(self, cond, x_T, lens):
+    def begin_ragged(self, cond, x_T, lens, *, noise=None, seeds=None, noise_rows=None, x_start=None, init_image=None, skip_timesteps=0):
         """Begin a RAGGED call (mmdm_begin_ragged): B items of different lengths in one batch.  cond [B, .]; lens: B ints; x_T: the items' frames
-        back to back [sum(lens), C], or a list of B tensors [T_i, C].  Every item's result is bit-identical to sampling it alone."""
+        back to back [sum(lens), C], or a list of B tensors [T_i, C].  Every item's result is bit-identical to sampling it alone.
+        With a keyword (mmdm_begin_ragged_opts; two-chain sampler; forms and shapes: pack_ragged_options) the same holds with begin()'s options: item b of
+        seeds=[...] equals sample(cond[b:b+1], x_b[None], seed=seeds[b], ...), and seeds=ONE int makes a batch of equal lengths equal to sample(cond, x,
+        seed=seed) of the uniform batch; noise / x_start / init_image are each item's own, packed or as lists."""
         lens = [int(v) for v in lens]
+        ro = None
+        if noise is not None or seeds is not None or noise_rows is not None or x_start is not None or init_image is not None or skip_timesteps:
+            ro = pack_ragged_options(lens, noise=noise, seeds=seeds, noise_rows=noise_rows, x_start=x_start, init_image=init_image, skip_timesteps=skip_timesteps)
         if isinstance(x_T, (list, tuple)):
             x_T = torch.cat([t.to(self.device, torch.float32).reshape(-1, t.shape[-1]) for t in x_T], 0)
         cond = cond.to(self.device, torch.float32).contiguous()
@@ -264,19 +345,42 @@ class Sampler:
         B = len(lens)
         if cond.shape[0] != B or x_T.dim() != 2 or x_T.shape[0] != sum(lens):
             raise ValueError(f"begin_ragged: cond rows {cond.shape[0]}, x_T {tuple(x_T.shape)} do not match {B} items of {sum(lens)} frames in all")
+        keep = [cond, x_T]
+        S, skip = self.schedule.num_timesteps, 0
+        opts = host = None
+        if ro is not None:
+            opts, skip = BeginRaggedOptions(), ro["skip_timesteps"]
+            for nm in ("noise", "x_start", "init_image"):
+                if ro[nm] is not None:
+                    t = ro[nm].to(self.device, torch.float32).contiguous()
+                    setattr(opts, nm, t.data_ptr())
+                    keep.append(t)
+            if ro["noise"] is not None:
+                opts.noise_source, opts.noise_steps = 1, ro["noise"].shape[0]
+            elif ro["seeds"] is not None:
+                host = ((C.c_ulonglong * B)(*ro["seeds"]), (C.c_int * B)(*ro["noise_rows"]))       # consumed before the call returns
+                opts.noise_source = 2
+                opts.item_seed, opts.item_noise_row = C.addressof(host[0]), C.addressof(host[1])
+            opts.skip_timesteps = skip
+            if (ro["init_image"] is not None or skip) and 0 <= skip < S:
+                a, b = self.schedule.q_sample_coefficients(S - 1 - skip)
+                opts.init_coef[0], opts.init_coef[1] = float(a), float(b)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        cond.record_stream(self.stream)
-        x_T.record_stream(self.stream)
+        for t in keep:
+            t.record_stream(self.stream)
         arr = (C.c_int * B)(*lens)
         with torch.cuda.device(self.device):
-            check(self.lib.mmdm_begin_ragged(self.h, C.c_void_p(cond.data_ptr()), C.c_void_p(x_T.data_ptr()), B, arr, self._s()), self.h)
+            if opts is None:
+                check(self.lib.mmdm_begin_ragged(self.h, C.c_void_p(cond.data_ptr()), C.c_void_p(x_T.data_ptr()), B, arr, self._s()), self.h)
+            else:
+                check(self.lib.mmdm_begin_ragged_opts(self.h, C.c_void_p(cond.data_ptr()), C.c_void_p(x_T.data_ptr()), B, arr, C.byref(opts), self._s()), self.h)
         rows, real, rag = C.c_int(), C.c_int(), C.c_int()
         check(self.lib.mmdm_call_rows(self.h, C.byref(rows), C.byref(real), C.byref(rag)), self.h)
-        self._keep = (cond, x_T)
+        self._keep = tuple(keep)
         self.B, self.T = B, max(lens)
         self.lens, self.rows = lens, rows.value
         self._hist = None
-        self._left = self._steps = self.schedule.num_timesteps
+        self._left = self._steps = S - skip
         return self
 
     def item_slices(self):
@@ -391,10 +495,13 @@ class Sampler:
         self.B, self.T, self.lens, self.rows = B, T, None, B * T
         self._left, self._steps = 0, self.schedule.num_timesteps
 
-    def sample_ragged_async(self, cond, x_T, lens, use_graph=True, history=None, history_every=1):
+    def sample_ragged_async(self, cond, x_T, lens, use_graph=True, history=None, history_every=1, *, eta=None, **opts):
         """A whole ragged sampling call queued on the sampler's stream (no host synchronisation): -> (list of per-item results [T_i, C], history
-        buffers [slots, 2, rows, C] or None, event).  Wait for the event before reading from the host or another stream."""
-        self.begin_ragged(cond, x_T, lens)
+        buffers [slots, 2, rows, C] or None, event).  Wait for the event before reading from the host or another stream.
+        eta as in sample(); the other keywords are begin_ragged()'s."""
+        if eta is not None and float(eta) != getattr(self, "eta", 0.0):
+            self.set_eta(eta)
+        self.begin_ragged(cond, x_T, lens, **opts)
         hist = self.set_history(history, history_every) if history else None
         self.run(None, use_graph)
         st = self.state(sync=False)
@@ -404,9 +511,9 @@ class Sampler:
             ev.record(self.stream)
         return [res[o:o + t] for o, t in self.item_slices()], hist, ev
 
-    def sample_ragged(self, cond, x_T, lens, use_graph=True):
-        """Ragged MixerDiffusion.ddim_sample_loop: list of B results [T_i, C]."""
-        items, _, ev = self.sample_ragged_async(cond, x_T, lens, use_graph)
+    def sample_ragged(self, cond, x_T, lens, use_graph=True, *, eta=None, **opts):
+        """Ragged MixerDiffusion.ddim_sample_loop: list of B results [T_i, C].  eta and the options: sample_ragged_async."""
+        items, _, ev = self.sample_ragged_async(cond, x_T, lens, use_graph, eta=eta, **opts)
         ev.synchronize()
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return items
