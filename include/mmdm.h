@@ -307,6 +307,40 @@ int mmdm_layernorm_f32(const float* x, const float* gamma, const float* beta, fl
 int mmdm_layernorm_split(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
                          int build, void* stream);
 
+/* Diagnostic entry points of the same kind: every row operation of a handle in either build of the row kernels (build as in mmdm_layernorm_split;
+ * anything else is MMDM_ERR_ARG).  They check arguments and dispatch to the code the handles run; tests/test_gpu_rowops.py holds both builds to
+ * float64 through them.
+ *   adaln:      mmdm_adaln_f32 with out_mode 0 fp32, 1 bf16, 2 the two fp16 planes [2][rows][D] (plane stride rows * D), 3 e4m3 bytes + row_scale
+ *               [rows] (max|y| / 448, 1 for a zero row).  row_seq != NULL: the ragged form -- rows_rag rows in all, row r takes ss row
+ *               row_seq[r] % ss_rows (DEVICE ints); nseq / T are then unused.
+ *   cond_silu:  mmdm_cond_silu_f32 (planes = 0, out fp32 [rows, D]) or the same values as two fp16 planes out[i], out[plane_stride + i].
+ *   mean_time:  mmdm_mean_time_f32, or with seq_off / seq_len (DEVICE ints [nseq], both or neither) the ragged form: sequence s = rows
+ *               [seq_off[s], seq_off[s] + seq_len[s]) of h, every length >= 1; T is then unused.
+ *   mdm_pack:   MDMDenoiser's sequence assembly, dst [nseq, T + 1, D]: dst[s, 0] = (cond[s, 0:D] + time_tab[*step_idx]) + pe[0] (cond row stride ldc),
+ *               dst[s, 1 + t] = src[s, t]; planes != NULL: the rows' two fp16 planes as well (D % 4 == 0, ldc % 4 == 0, 16-byte aligned rows).
+ *   mdm_unpack: dst[s, t] = src[s, 1 + t], src [nseq, T + 1, D].
+ *   _rag:       the same two passes on a ragged batch of B items in `groups` groups, gpp groups per person.  Frame rows of a group: the items'
+ *               frames back to back in fr_rows rows; token rows: every item's token in front of its frames, in tk_rows rows.  Each space is four
+ *               DEVICE int arrays: row_item [rows] (-1 = padding row), row_pos [rows] (index inside the item; token space: 0 = the token, k >= 1 =
+ *               frame k - 1), item_off [B] (first row of an item), item_len [B].  pack: token of item i in group g = (cond[(g % gpp) B + i,
+ *               (g / gpp) D + 0:D] + time_tab[*step_idx]) + pe[0], frame rows from src [groups, fr_rows, D], padding rows zeros (planes too);
+ *               unpack: dst [groups, fr_rows, D] from src [groups, tk_rows, D], padding rows zeros. */
+int mmdm_rowop_adaln(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_mode, float* row_scale, int nseq, int T, int D,
+                     const int* row_seq, int rows_rag, int build, void* stream);
+int mmdm_rowop_cond_silu(const float* time_tab, const int* step_idx, const float* txt, void* out, int planes, int64_t plane_stride, int rows, int D,
+                         int build, void* stream);
+int mmdm_rowop_mean_time(const float* h, float* out, int nseq, int T, const int* seq_off, const int* seq_len, int D, int build, void* stream);
+int mmdm_rowop_mdm_pack(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                        int64_t plane_stride, int nseq, int T, int D, int build, void* stream);
+int mmdm_rowop_mdm_unpack(const float* src, float* dst, int nseq, int T, int D, int build, void* stream);
+int mmdm_rowop_mdm_pack_rag(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                            int64_t plane_stride, int groups, int gpp, int D, int B, int fr_rows, const int* fr_row_item, const int* fr_row_pos,
+                            const int* fr_item_off, const int* fr_item_len, int tk_rows, const int* tk_row_item, const int* tk_row_pos,
+                            const int* tk_item_off, const int* tk_item_len, int build, void* stream);
+int mmdm_rowop_mdm_unpack_rag(const float* src, float* dst, int groups, int D, int B, int fr_rows, const int* fr_row_item, const int* fr_row_pos,
+                              const int* fr_item_off, const int* fr_item_len, int tk_rows, const int* tk_row_item, const int* tk_row_pos,
+                              const int* tk_item_off, const int* tk_item_len, int build, void* stream);
+
 /* out[b,l,:] = table[tokens[b,l],:] + pos[l,:]; tokens: DEVICE int32 [n,L], clamped to [0, vocab).
  * Replaces token_embedding(text) + positional_embedding  src/models/mixermdm.py:298-299. */
 int mmdm_token_embed_f32(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, void* stream);

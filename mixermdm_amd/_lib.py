@@ -119,7 +119,14 @@ SYMBOLS = {
     "mmdm_attention_ragged_opts_f32": (_I, [_VP, _I, _VP, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "mmdm_attention_split_ragged": (_I, [_VP, _I, C.c_int64, _VP, _I, C.c_int64, _VP, _I, C.c_int64, _VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "mmdm_layernorm_split": (_I, [_VP, _VP, _VP, _VP, _VP, C.c_int64, _I, _I, C.c_float, _I, _VP]),
-    "mmdm_set_history": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "mmdm_rowop_adaln": (_I, [_VP, _VP, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _I, _I, _VP]),
+    "mmdm_rowop_cond_silu": (_I, [_VP, _VP, _VP, _VP, _I, C.c_int64, _I, _I, _I, _VP]),
+    "mmdm_rowop_mean_time": (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _I, _VP]),
+    "mmdm_rowop_mdm_pack": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, C.c_int64, _I, _I, _I, _I, _VP]),
+    "mmdm_rowop_mdm_unpack": (_I, [_VP, _VP, _I, _I, _I, _I, _VP]),
+    "mmdm_rowop_mdm_pack_rag": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, C.c_int64, _I, _I, _I, _I] + [_I, _VP, _VP, _VP, _VP] * 2 + [_I, _VP]),
+    "mmdm_rowop_mdm_unpack_rag": (_I, [_VP, _VP, _I, _I, _I] + [_I, _VP, _VP, _VP, _VP] * 2 + [_I, _VP]),
+    "mmdm_set_history":(_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I]),
     "mmdm_run": (_I, [_VP, _I, _I, _VP]),
     "mmdm_seek": (_I, [_VP, _I, _VP]),
     "mmdm_graph_stats": (_I, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_I)]),

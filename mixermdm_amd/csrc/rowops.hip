@@ -665,4 +665,98 @@ extern "C" int mmdm_influence_head_f32(const float* h, const float* Wout, const 
     hipLaunchKernelGGL(influence_head_kernel, dim3((rows + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), h, Wout, bout, w, rows, D, nw);
     return mmdm_check_launch("influence_head");
 }
+
+// Diagnostic entry points (include/mmdm.h, beside mmdm_layernorm_split): every row operation in either build, for tests/test_gpu_rowops.py.  Argument
+// checks and dispatch only -- the kernels and their launch code are the ones the handles run (ROWOP in mmdm.hip).
+#define ROWOP_BUILD(what)                                                                                         \
+    if (build != 0 && build != 1) return mmdm_set_error(MMDM_ERR_ARG, what ": build must be 0 or 1")
+
+extern "C" int mmdm_rowop_adaln(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_mode, float* row_scale, int nseq, int T, int D,
+                                const int* row_seq, int rows_rag, int build, void* stream) {
+    ROWOP_BUILD("mmdm_rowop_adaln");
+    if (out_mode < 0 || out_mode > 3) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_adaln: output mode must be 0 (fp32), 1 (bf16), 2 (two fp16 planes) or 3 (fp8 + row_scale)");
+    if (out_mode == 3 && !row_scale) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_adaln: null row_scale");
+    if (row_seq && rows_rag < 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_adaln: rows_rag=%d", rows_rag);
+    return build ? mmdm_adaln_any_nopk(h, ss, ss_ld, ss_rows, out, out_mode, row_scale, nseq, T, D, stream, row_seq, rows_rag)
+                 : mmdm_adaln_any(h, ss, ss_ld, ss_rows, out, out_mode, row_scale, nseq, T, D, stream, row_seq, rows_rag);
+}
+
+extern "C" int mmdm_rowop_cond_silu(const float* time_tab, const int* step_idx, const float* txt, void* out, int planes, int64_t plane_stride, int rows, int D,
+                                    int build, void* stream) {
+    ROWOP_BUILD("mmdm_rowop_cond_silu");
+    if (!planes) return build ? mmdm_cond_silu_f32_nopk(time_tab, step_idx, txt, static_cast<float*>(out), rows, D, stream)
+                              : mmdm_cond_silu_f32(time_tab, step_idx, txt, static_cast<float*>(out), rows, D, stream);
+    if (rows == 0) return MMDM_OK;
+    if (!time_tab || !step_idx || !txt || !out || rows < 0 || D <= 0 || plane_stride < (int64_t)rows * D)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_cond_silu: bad arguments rows=%d D=%d plane stride=%lld", rows, D, (long long)plane_stride);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return build ? mmdm_cond_silu_planes_nopk(time_tab, step_idx, txt, static_cast<_Float16*>(out), (size_t)plane_stride, rows, D, st)
+                 : mmdm_cond_silu_planes(time_tab, step_idx, txt, static_cast<_Float16*>(out), (size_t)plane_stride, rows, D, st);
+}
+
+extern "C" int mmdm_rowop_mean_time(const float* h, float* out, int nseq, int T, const int* seq_off, const int* seq_len, int D, int build, void* stream) {
+    ROWOP_BUILD("mmdm_rowop_mean_time");
+    if (!seq_off && !seq_len) return build ? mmdm_mean_time_f32_nopk(h, out, nseq, T, D, stream) : mmdm_mean_time_f32(h, out, nseq, T, D, stream);
+    if (nseq == 0) return MMDM_OK;
+    if (!h || !out || !seq_off || !seq_len || nseq < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mean_time: bad arguments (ragged: seq_off AND seq_len)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return build ? mmdm_mean_time_rag_nopk(h, out, nseq, seq_off, seq_len, D, st) : mmdm_mean_time_rag(h, out, nseq, seq_off, seq_len, D, st);
+}
+
+extern "C" int mmdm_rowop_mdm_pack(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                                   int64_t plane_stride, int nseq, int T, int D, int build, void* stream) {
+    ROWOP_BUILD("mmdm_rowop_mdm_pack");
+    if (nseq == 0) return MMDM_OK;
+    if (!src || !cond || !time_tab || !step_idx || !pe || !dst || nseq < 0 || T < 0 || D <= 0 || ldc < D || (planes && plane_stride < (int64_t)nseq * (T + 1) * D))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_pack: bad arguments nseq=%d T=%d D=%d ldc=%d", nseq, T, D, ldc);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (planes) return build ? mmdm_mdm_pack_planes_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, nseq, T, D, st)
+                             : mmdm_mdm_pack_planes(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, nseq, T, D, st);
+    return build ? mmdm_mdm_pack_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, nseq, T, D, st) : mmdm_mdm_pack(src, cond, ldc, time_tab, step_idx, pe, dst, nseq, T, D, st);
+}
+
+extern "C" int mmdm_rowop_mdm_unpack(const float* src, float* dst, int nseq, int T, int D, int build, void* stream) {
+    ROWOP_BUILD("mmdm_rowop_mdm_unpack");
+    if (nseq == 0 || T == 0) return MMDM_OK;
+    if (!src || !dst || nseq < 0 || T < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_unpack: bad arguments nseq=%d T=%d D=%d", nseq, T, D);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return build ? mmdm_mdm_unpack_nopk(src, dst, nseq, T, D, st) : mmdm_mdm_unpack(src, dst, nseq, T, D, st);
+}
+
+// the two row spaces of a ragged batch as the caller's device arrays (kernels.h mmdm_rag): frame rows fr_*, token rows tk_*
+#define ROWOP_RAG_CHECK(what)                                                                                                                              \
+    if (!fr_row_item || !fr_row_pos || !fr_item_off || !fr_item_len || !tk_row_item || !tk_row_pos || !tk_item_off || !tk_item_len || B <= 0 ||          \
+        B > MMDM_RAG_MAX_ITEMS || fr_rows <= 0 || tk_rows <= 0)                                                                                            \
+        return mmdm_set_error(MMDM_ERR_ARG, what ": bad row maps B=%d frame rows=%d token rows=%d", B, fr_rows, tk_rows);                                \
+    const mmdm_rag fr{fr_row_item, fr_row_pos, fr_item_off, fr_item_len, B, fr_rows}, tk{tk_row_item, tk_row_pos, tk_item_off, tk_item_len, B, tk_rows}
+
+extern "C" int mmdm_rowop_mdm_pack_rag(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                                       int64_t plane_stride, int groups, int gpp, int D, int B, int fr_rows, const int* fr_row_item, const int* fr_row_pos,
+                                       const int* fr_item_off, const int* fr_item_len, int tk_rows, const int* tk_row_item, const int* tk_row_pos,
+                                       const int* tk_item_off, const int* tk_item_len, int build, void* stream) {
+    ROWOP_BUILD("mmdm_rowop_mdm_pack_rag");
+    if (groups == 0) return MMDM_OK;
+    ROWOP_RAG_CHECK("mmdm_rowop_mdm_pack_rag");
+    if (!src || !cond || !time_tab || !step_idx || !pe || !dst || groups < 0 || gpp <= 0 || D <= 0 || ldc < (groups + gpp - 1) / gpp * D ||
+        (planes && plane_stride < (int64_t)groups * tk_rows * D))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_pack_rag: bad arguments groups=%d gpp=%d D=%d ldc=%d", groups, gpp, D, ldc);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (planes) return build ? mmdm_mdm_pack_rag_planes_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, groups, gpp, D, fr, tk, st)
+                             : mmdm_mdm_pack_rag_planes(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, groups, gpp, D, fr, tk, st);
+    return build ? mmdm_mdm_pack_rag_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, fr, tk, st)
+                 : mmdm_mdm_pack_rag(src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, fr, tk, st);
+}
+
+extern "C" int mmdm_rowop_mdm_unpack_rag(const float* src, float* dst, int groups, int D, int B, int fr_rows, const int* fr_row_item, const int* fr_row_pos,
+                                         const int* fr_item_off, const int* fr_item_len, int tk_rows, const int* tk_row_item, const int* tk_row_pos,
+                                         const int* tk_item_off, const int* tk_item_len, int build, void* stream) {
+    ROWOP_BUILD("mmdm_rowop_mdm_unpack_rag");
+    if (groups == 0) return MMDM_OK;
+    ROWOP_RAG_CHECK("mmdm_rowop_mdm_unpack_rag");
+    if (!src || !dst || groups < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_unpack_rag: bad arguments groups=%d D=%d", groups, D);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return build ? mmdm_mdm_unpack_rag_nopk(src, dst, groups, D, fr, tk, st) : mmdm_mdm_unpack_rag(src, dst, groups, D, fr, tk, st);
+}
+#undef ROWOP_RAG_CHECK
+#undef ROWOP_BUILD
 #endif

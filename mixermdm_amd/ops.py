@@ -46,14 +46,36 @@ def linear(x, weight, bias=None, epilogue="bias", extra=None, period=0, out=None
     return out.reshape(*x.shape[:-1], N) if x.is_contiguous() else out
 
 
-def adaln(h, ss, ss_rows=None):
-    """h [nseq, T, D]; ss [rows, 2D] (scale | shift); row(s) = s % ss_rows."""
-    _chk(h, ss)
-    nseq, T, D = h.shape
+_ADALN_OUT = {"f32": 0, "bf16": 1, "planes": 2, "fp8": 3}
+
+
+def adaln(h, ss, ss_rows=None, build=0, out="f32", row_seq=None):
+    """h [nseq, T, D]; ss [rows, 2D] (scale | shift); row(s) = s % ss_rows.
+    build: 0 = the row kernels of fp32 handles and of the stateless entry points, 1 = the build without packed-fp32 instructions that fp32_split / bf16 /
+    bf16_fp8 handles run (mmdm_rowop_adaln).  out: "f32", "bf16", "planes" (float16 [2, *h.shape], the split of the fp32 row) or "fp8" (returns
+    (float8_e4m3fn like h, row_scale fp32 [rows])).  row_seq: int32 device tensor [rows] -- the ragged form on h [rows, D], row r takes ss row
+    row_seq[r] % ss_rows."""
+    _chk(h, ss, row_seq)
+    mode = _ADALN_OUT[out]
     h = h.contiguous()
-    out = torch.empty_like(h)
-    check(load_library().mmdm_adaln_f32(_p(h), _p(ss), ss.stride(0), ss_rows or ss.shape[0], _p(out), nseq, T, D, _stream()))
-    return out
+    D = h.shape[-1]
+    if mode == 0 and build == 0 and row_seq is None:
+        nseq, T, _ = h.shape
+        o = torch.empty_like(h)
+        check(load_library().mmdm_adaln_f32(_p(h), _p(ss), ss.stride(0), ss_rows or ss.shape[0], _p(o), nseq, T, D, _stream()))
+        return o
+    if row_seq is not None:
+        assert h.dim() == 2 and row_seq.dtype == torch.int32 and row_seq.is_contiguous() and row_seq.numel() == h.shape[0]
+        nseq, T, rows = 0, 0, h.shape[0]
+    else:
+        nseq, T, _ = h.shape
+        rows = nseq * T
+    shape = (2, *h.shape) if mode == 2 else h.shape
+    o = torch.empty(shape, device=h.device, dtype=(torch.float32, torch.bfloat16, torch.float16, torch.uint8)[mode])
+    scale = torch.empty(rows, device=h.device, dtype=torch.float32) if mode == 3 else None
+    check(load_library().mmdm_rowop_adaln(_p(h), _p(ss), ss.stride(0), ss_rows or ss.shape[0], C.c_void_p(o.data_ptr()), mode, _p(scale), nseq, T, D,
+                                          _p(row_seq), rows if row_seq is not None else 0, int(build), _stream()))
+    return (o.view(torch.float8_e4m3fn), scale) if mode == 3 else o
 
 
 def attention(q, k, v, num_heads, kv_seq_shift=0, zero_key=True, causal=False, key_padding_mask=None):
@@ -118,9 +140,11 @@ def layernorm_split(x, weight, bias, eps=1e-5, build=0, planes=True):
     x = x.contiguous()
     out = torch.empty_like(x)
     D = x.shape[-1]
-    pl = torch.empty(2, *x.shape, device=x.device, dtype=torch.float16) if planes else None
-    check(load_library().mmdm_layernorm_split(_p(x), _p(weight), _p(bias), _p(out), _p(pl), x.numel(), x.numel() // D, D, float(eps), int(build), _stream()))
-    return out, pl
+    n = x.numel()
+    stride = (n + 7) // 8 * 8                # the plane stride is a multiple of 8 elements (a 4-element tensor gets a padded buffer and a view of it)
+    buf = torch.empty(2, stride, device=x.device, dtype=torch.float16) if planes else None
+    check(load_library().mmdm_layernorm_split(_p(x), _p(weight), _p(bias), _p(out), _p(buf), stride, n // D, D, float(eps), int(build), _stream()))
+    return out, (buf[:, :n].reshape(2, *x.shape) if planes else None)
 
 
 def token_embed(table, tokens, pos):
@@ -164,10 +188,22 @@ def encoder_layer_(x, w, num_heads, norm_first=False, activation="gelu", causal=
     return x
 
 
-def cond_silu(time_tab, step_idx, txt):
+def cond_silu(time_tab, step_idx, txt, build=0, planes=False, out=None):
+    """silu(time_tab[*step_idx] + txt) for txt [rows, D].  build as in `adaln`.  planes: the values as their two fp16 planes instead (float16; `out`, if
+    given, is a contiguous float16 tensor [2, n >= rows * D] whose row length n is the plane stride)."""
     _chk(time_tab, step_idx, txt)
-    out = torch.empty_like(txt)
-    check(load_library().mmdm_cond_silu_f32(_p(time_tab), _p(step_idx), _p(txt), _p(out), txt.shape[0], txt.shape[1], _stream()))
+    rows, D = txt.shape
+    if not planes:
+        out = torch.empty_like(txt)
+        if build == 0:
+            check(load_library().mmdm_cond_silu_f32(_p(time_tab), _p(step_idx), _p(txt), _p(out), rows, D, _stream()))
+        else:
+            check(load_library().mmdm_rowop_cond_silu(_p(time_tab), _p(step_idx), _p(txt), _p(out), 0, 0, rows, D, int(build), _stream()))
+        return out
+    if out is None:
+        out = torch.empty(2, rows * D, device=txt.device, dtype=torch.float16)
+    assert out.is_cuda and out.dtype == torch.float16 and out.dim() == 2 and out.shape[0] == 2 and out.is_contiguous()
+    check(load_library().mmdm_rowop_cond_silu(_p(time_tab), _p(step_idx), _p(txt), C.c_void_p(out.data_ptr()), 1, out.shape[1], rows, D, int(build), _stream()))
     return out
 
 
@@ -195,12 +231,95 @@ def influence_head(h, weight, bias):
     return w
 
 
-def mean_time(h):
-    _chk(h)
+def mean_time(h, build=0, seq_off=None, seq_len=None):
+    """Mean over time of h [nseq, T, D]; with seq_off / seq_len (int32 device tensors [nseq]) the ragged form on h [rows, D]: sequence s = rows
+    [seq_off[s], seq_off[s] + seq_len[s]).  build as in `adaln`."""
+    _chk(h, seq_off, seq_len)
+    h = h.contiguous()
+    if seq_off is not None or seq_len is not None:
+        assert h.dim() == 2 and seq_off.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_off.numel() == seq_len.numel()
+        nseq, D = seq_off.numel(), h.shape[1]
+        out = torch.empty(nseq, D, device=h.device, dtype=torch.float32)
+        check(load_library().mmdm_rowop_mean_time(_p(h), _p(out), nseq, 0, _p(seq_off), _p(seq_len), D, int(build), _stream()))
+        return out
     nseq, T, D = h.shape
     out = torch.empty(nseq, D, device=h.device, dtype=torch.float32)
-    check(load_library().mmdm_mean_time_f32(_p(h.contiguous()), _p(out), nseq, T, D, _stream()))
+    if build == 0:
+        check(load_library().mmdm_mean_time_f32(_p(h), _p(out), nseq, T, D, _stream()))
+    else:
+        check(load_library().mmdm_rowop_mean_time(_p(h), _p(out), nseq, T, None, None, D, int(build), _stream()))
     return out
+
+
+def mdm_pack(src, cond, time_tab, step_idx, pe, build=0, planes=False):
+    """MDMDenoiser's sequence assembly: src [nseq, T, D], cond [nseq, D] (may be a column slice of a wider tensor) -> dst [nseq, T + 1, D] with the
+    conditioning token (cond + time_tab[*step_idx]) + pe[0] in front of every sequence.  planes: returns (dst, float16 [2, nseq, T + 1, D]).
+    build as in `adaln`."""
+    _chk(src, cond, time_tab, step_idx, pe)
+    src = src.contiguous()
+    nseq, T, D = src.shape
+    assert cond.shape == (nseq, D) and cond.stride(1) == 1 and time_tab.is_contiguous() and pe.is_contiguous()
+    dst = torch.empty(nseq, T + 1, D, device=src.device, dtype=torch.float32)
+    n = dst.numel()
+    stride = (n + 7) // 8 * 8                # the plane stride is a multiple of 8 elements
+    buf = torch.empty(2, stride, device=src.device, dtype=torch.float16) if planes else None
+    check(load_library().mmdm_rowop_mdm_pack(_p(src), _p(cond), cond.stride(0), _p(time_tab), _p(step_idx), _p(pe), _p(dst), _p(buf), stride,
+                                             nseq, T, D, int(build), _stream()))
+    return (dst, buf[:, :n].reshape(2, nseq, T + 1, D)) if planes else dst
+
+
+def mdm_unpack(src, build=0):
+    """src [nseq, T + 1, D] -> [nseq, T, D] without the conditioning token."""
+    _chk(src)
+    src = src.contiguous()
+    nseq, T1, D = src.shape
+    dst = torch.empty(nseq, T1 - 1, D, device=src.device, dtype=torch.float32)
+    check(load_library().mmdm_rowop_mdm_unpack(_p(src), _p(dst), nseq, T1 - 1, D, int(build), _stream()))
+    return dst
+
+
+def _rag_args(maps, rows):
+    row_item, row_pos, item_off, item_len = maps
+    _chk(*maps)
+    for t in maps:
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert row_item.numel() == rows and row_pos.numel() == rows and item_off.numel() == item_len.numel()
+    return [rows, _p(row_item), _p(row_pos), _p(item_off), _p(item_len)]
+
+
+def mdm_pack_rag(src, cond, time_tab, step_idx, pe, fr, tk, tk_rows, gpp, build=0, dst=None, planes=None):
+    """mdm_pack on a ragged batch (mmdm_rowop_mdm_pack_rag): src [groups, fr_rows, D]; fr / tk = (row_item, row_pos, item_off, item_len) int32 device
+    tensors of the frame and the token row space; cond [gpp * B, >= persons * D].  dst [groups, tk_rows, D] (or more rows: what lies behind the
+    last group is not written) is created unless given; planes: a contiguous float16 [2, n] tensor (n >= groups * tk_rows * D = the plane stride).
+    Returns dst."""
+    _chk(src, cond, time_tab, step_idx, pe)
+    src = src.contiguous()
+    groups, fr_rows, D = src.shape
+    B = fr[2].numel()
+    assert cond.stride(1) == 1 and cond.shape[0] >= gpp * B
+    if dst is None:
+        dst = torch.empty(groups, tk_rows, D, device=src.device, dtype=torch.float32)
+    assert dst.is_contiguous() and dst.numel() >= groups * tk_rows * D
+    stride = 0
+    if planes is not None:
+        assert planes.is_cuda and planes.dtype == torch.float16 and planes.dim() == 2 and planes.shape[0] == 2 and planes.is_contiguous()
+        stride = planes.shape[1]
+    check(load_library().mmdm_rowop_mdm_pack_rag(_p(src), _p(cond), cond.stride(0), _p(time_tab), _p(step_idx), _p(pe), _p(dst), _p(planes), stride,
+                                                 groups, int(gpp), D, B, *_rag_args(fr, fr_rows), *_rag_args(tk, tk_rows), int(build), _stream()))
+    return dst
+
+
+def mdm_unpack_rag(src, fr, tk, fr_rows, build=0, dst=None):
+    """mdm_unpack on a ragged batch: src [groups, tk_rows, D] -> dst [groups, fr_rows, D] (created unless given), padding frame rows zeros."""
+    _chk(src)
+    src = src.contiguous()
+    groups, tk_rows, D = src.shape
+    if dst is None:
+        dst = torch.empty(groups, fr_rows, D, device=src.device, dtype=torch.float32)
+    assert dst.is_contiguous() and dst.numel() >= groups * fr_rows * D
+    check(load_library().mmdm_rowop_mdm_unpack_rag(_p(src), _p(dst), groups, D, fr[2].numel(), *_rag_args(fr, fr_rows), *_rag_args(tk, tk_rows),
+                                                   int(build), _stream()))
+    return dst
 
 
 def blend_cfg(out1, out2, w, mode, cfg_scale, force=None, want_hist=False):
@@ -464,8 +583,10 @@ def linear_fp8(xq, x_scale, wq, w_scale, bias=None, epilogue="bias", extra=None,
     return out.reshape(*xq.shape[:-1], N)
 
 
-def adaln_fp8(h, ss, ss_rows=None):
-    """AdaLN apply with an fp8 result: (q float8_e4m3fn [nseq, T, D], row_scale fp32 [nseq*T])."""
+def adaln_fp8(h, ss, ss_rows=None, build=0):
+    """AdaLN apply with an fp8 result: (q float8_e4m3fn [nseq, T, D], row_scale fp32 [nseq*T]).  build as in `adaln`."""
+    if build:
+        return adaln(h, ss, ss_rows, build=build, out="fp8")
     _chk(h, ss)
     nseq, T, D = h.shape
     h = h.contiguous()
