@@ -209,6 +209,18 @@ int mmdm_attention_bf16(const void* Qp, int ldq, const void* Kp, int ldk, const 
 int mmdm_attention_split(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, const void* Vp, int ldv, int64_t v_plane,
                          void* O, int ldo, int out_mode, int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, void* stream);
 
+/* mmdm_attention_split with a KEY-PADDING mask, with the semantics of mmdm_attention_masked_f32: key_valid is a DEVICE byte array [mask_rows, Tk],
+ * 1 = the key exists, 0 = the key is ignored (logit -inf); key sequence kvseq = (s + kv_seq_shift) % nseq reads row kvseq % mask_rows.  The zero key
+ * is never masked: a query whose keys are all masked gets exactly 0.  The K / V planes of masked keys must be FINITE.  key_valid == NULL is
+ * mmdm_attention_split, bit for bit (the same kernel instantiation); a mask runs a separate instantiation of the two-plane kernel: with an all-valid
+ * mask it gives the bits of the unmasked call, and a mask that keeps the first L keys gives, in the first L query rows of self-attention, the bits of
+ * mmdm_attention_split at T = L.  out_mode 0 (fp32) or 2 (the two fp16 planes).  dh = 64 or 128.
+ * MMDM_ERR_UNSUPPORTED: a mask together with MMDM_ATTN_NO_ZERO_KEY / MMDM_ATTN_CAUSAL (without the zero key an all-masked first chunk would form NaN);
+ * mmdm_attention_split_ragged takes no mask (a ragged batch carries its lengths instead). */
+int mmdm_attention_split_masked(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, const void* Vp, int ldv, int64_t v_plane,
+                                void* O, int ldo, int out_mode, int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift,
+                                const unsigned char* key_valid, int mask_rows, void* stream);
+
 /* mmdm_attention_split over a RAGGED batch (sequence description as mmdm_attention_ragged_f32; O rows / planes of total_rows rows).  flags = 0 or
  * MMDM_ATTN_NO_ZERO_KEY (the MDM encoder of a precision-2 handle on a ragged batch: plain softmax over each token sequence's own keys; every sequence
  * needs >= 1 key).  Per sequence bit-identical to mmdm_attention_split with the same flags on that sequence alone; rows of O outside every sequence are
@@ -493,8 +505,11 @@ int mmdm_prepare(mmdm_handle h);
  *   - captured step graphs read the mask through the handle's buffers: replacing the VALUES needs no re-capture; masked and unmasked steps
  *     of the same (B, T, S) are different cache entries and never replay each other.
  * MMDM_ERR_ARG: rows outside [1, 2 * max_batch], T outside [1, max_frames], a row with no valid frame (the reference would index frame -1).
- * MMDM_ERR_UNSUPPORTED (never a silent unmasked run): precision 1-3 handles (the 16-bit attention forms take no mask), model1_kind = 1 (the
- * MDM encoder's src_key_padding_mask), single_only 2 / 3 (and so which = 3); with a mask set, mmdm_begin_ragged is MMDM_ERR_UNSUPPORTED. */
+ * Precision 0 and 2 (fp32_split) handles take a mask: the fp32 attention kernel and the two-plane kernel of the fp32-split mode each have a masked
+ * instantiation (mmdm_attention_masked_f32, mmdm_attention_split_masked), and a precision-2 stack whose head size is not 64 / 128 runs the fp32 one.
+ * MMDM_ERR_UNSUPPORTED (never a silent unmasked run): precision 1 and 3 handles (the bf16 attention forms take no mask), model1_kind = 1 (the
+ * MDM encoder's src_key_padding_mask, in either precision), single_only 2 / 3 (and so which = 3); with a mask set, mmdm_begin_ragged is
+ * MMDM_ERR_UNSUPPORTED. */
 int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, int T);
 
 /* Begin a sampling call: cond [B, 8*text_dim] (layout src/models/mixermdm.py:342-354) or [B, text_dim] (single_only),

@@ -536,11 +536,19 @@ __device__ __forceinline__ void store_out(const AttnArgs& p, size_t idx, float y
 #ifndef QKP_TWO_CHAINS
 #define QKP_TWO_CHAINS 1              // (0: the four-chain form of rounds 2-5, for A/B builds: 55.7 vs 52.0 us at 64 x 8 x 300 x 128, 61.8 vs 60.8 at dh = 64)
 #endif
-template <int DH, int NP, bool PVB = false, bool H2 = false, bool RAG = false>
+// MASK (H2 only): key-padding mask (AttnArgs::key_valid), as attn_mfma_kernel<..., MASK> has it and with the same lane layout (st[0][r] is key c0 + 4g + r of
+// query lq) -- its own instantiation, so that the unmasked chunk loop holds no trace of it.  One validity byte per lane and chunk (key c0 + lq), requested
+// one chunk ahead: behind the barrier and in front of the next stage's DMA, so the loop's vmcnt(0) of the next iteration covers it.  A ballot -- behind the
+// wave-uniform `q0 >= G.Tq` exit, so whole waves execute it -- turns the bytes into 16 wave-uniform bits, and a masked score becomes -inf exactly where a key
+// past Tk does.  Nothing else is new: the probability 2^-inf = 0 splits into ph = pl = phs = 0, a masked key never raises the deferred maximum (the zero
+// key keeps m_run >= 0, so p <= 16 holds as before), and a chunk whose keys are all masked has cmax = -inf: m_new = m_run, alpha = 1, (m, l, O) stay as
+// they were (O += 0 * V: K / V planes of masked keys must be FINITE).  With every key masked the zero key alone remains and the output is exactly 0.
+template <int DH, int NP, bool PVB = false, bool H2 = false, bool RAG = false, bool MASK = false>
 __global__ __launch_bounds__(256, H2 ? 4 : 2) void attn_qkp_kernel(AttnArgs p) {      // H2: four waves per SIMD (128 registers)
 #if defined(__HIP_DEVICE_COMPILE__)          // the buffer-resource type of the LDS-DMA builtin exists in the device pass only
     static_assert(!PVB || NP == 1 || H2, "bf16 P.V goes with bf16 scores");
     static_assert(!H2 || (NP == 2 && PVB), "the fp16 two-plane form covers Q K^T and P.V together");
+    static_assert(!MASK || (H2 && !RAG), "the key mask exists for the uniform two-plane form only");
     typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
     constexpr int NVP = H2 ? 2 : 1;             // V planes (16-bit V)
     constexpr int VPLANE = KC * DH / 2;         // floats per 16-bit V plane
@@ -638,6 +646,14 @@ __global__ __launch_bounds__(256, H2 ? 4 : 2) void attn_qkp_kernel(AttnArgs p) {
         const int last_q = min(qt * QB + QB - 1, G.Tq - 1);
         nchunks = min(nchunks, last_q / KC + 1);
     }
+    // MASK: this lane's validity byte of a chunk (key c0 + lq; the index is clamped, nothing is read outside the row).  The load's result is not touched
+    // before the ballot of its chunk -- the "0 past Tk" is applied there: a select right behind the load would make the compiler wait for it in
+    // front of the stage's DMA requests.
+    [[maybe_unused]] const unsigned char* mrow = nullptr;
+    if constexpr (MASK) mrow = p.key_valid + (size_t)(kvseq % p.mask_rows) * G.Tk;
+    [[maybe_unused]] auto mask_byte = [&](int c0) -> int { return mrow[min(c0 + lq, G.Tk - 1)]; };
+    [[maybe_unused]] int mb_next = 0;
+    if constexpr (MASK) mb_next = mask_byte(0);          // (Tk >= 1: chunk 0 exists; older than every DMA piece, so the loop's first vmcnt(0) covers it)
     stage(0, 0);
     // the stage index is a compile-time constant (the body exists twice): fragment reads address LDS with an immediate
     for (int cb2 = 0; cb2 < nchunks; cb2 += 2) {
@@ -648,6 +664,8 @@ __global__ __launch_bounds__(256, H2 ? 4 : 2) void attn_qkp_kernel(AttnArgs p) {
         const int c0 = ci * KC;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        [[maybe_unused]] const int mb = mb_next;
+        if constexpr (MASK) { if (ci + 1 < nchunks) mb_next = mask_byte(c0 + KC); }
         if (ci + 1 < nchunks) stage(c0 + KC, cur ^ 1);
         const float* Ks = smem + cur * STAGE;
         const float* Vs = Ks + NP * KPLANE;
@@ -705,6 +723,12 @@ __global__ __launch_bounds__(256, H2 ? 4 : 2) void attn_qkp_kernel(AttnArgs p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (c0 + 4 * g + r > kmax) st[0][r] = -INFINITY;
+        }
+        if constexpr (MASK) {                           // bit k of the ballot = lane k = key c0 + k
+            const unsigned live = (unsigned)__builtin_amdgcn_ballot_w64(mb != 0 && c0 + lq < G.Tk) >> (4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (!((live >> r) & 1u)) st[0][r] = -INFINITY;
         }
         float cmax = vmax3(st[0][0], st[0][1], vmax(st[0][2], st[0][3]));
         cmax = rows_max(cmax);
@@ -1010,6 +1034,10 @@ int launch_qkp(const AttnArgs& a, hipStream_t st) {
         // ragged batches: the production forms only (all-bf16 and the fp16 planes); the three-plane / fp32-V experiments stay uniform
         if constexpr (PVB) hipLaunchKernelGGL((attn_qkp_kernel<DH, NP, PVB, H2, true>), dim3(8 * a.pairs_per_xcd * a.qtiles), dim3(256), smem_bytes, st, a);
         else return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention on ragged batches: this operand form has no ragged instantiation");
+    } else if (a.key_valid) {
+        // key-padding mask: the production two-plane form only (mmdm_attention_planes_ex has refused the rest by name)
+        if constexpr (H2) hipLaunchKernelGGL((attn_qkp_kernel<DH, NP, PVB, H2, false, true>), dim3(8 * a.pairs_per_xcd * a.qtiles), dim3(256), smem_bytes, st, a);
+        else return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention with a key mask: this operand form has no masked instantiation");
     } else hipLaunchKernelGGL((attn_qkp_kernel<DH, NP, PVB, H2>), dim3(8 * a.pairs_per_xcd * a.qtiles), dim3(256), smem_bytes, st, a);
     return mmdm_check_launch("attn_qkp");
 }
@@ -1260,6 +1288,15 @@ extern "C" int mmdm_attention_split(const void* Qp, int ldq, int64_t q_plane, co
     return mmdm_attention_planes_ex(Qp, ldq, q_plane, Kp, ldk, k_plane, 2, nullptr, 0, Vp, ldv, v_plane, O, ldo, out_mode, flags, nseq, Tq, Tk, H, dh, kv_seq_shift, stream);
 }
 
+extern "C" int mmdm_attention_split_masked(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, const void* Vp, int ldv, int64_t v_plane,
+                                           void* O, int ldo, int out_mode, int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift,
+                                           const unsigned char* key_valid, int mask_rows, void* stream) {
+    if (!Vp) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_split_masked: V is null");
+    if (out_mode != 0 && out_mode != 2) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_split_masked: out_mode %d (0 = fp32, 2 = the two fp16 planes)", out_mode);
+    return mmdm_attention_planes_ex(Qp, ldq, q_plane, Kp, ldk, k_plane, 2, nullptr, 0, Vp, ldv, v_plane, O, ldo, out_mode, flags, nseq, Tq, Tk, H, dh, kv_seq_shift, stream,
+                                    nullptr, key_valid, mask_rows);
+}
+
 // mmdm_attention_split over a ragged batch (sequence description as mmdm_attention_ragged_f32)
 extern "C" int mmdm_attention_split_ragged(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, const void* Vp, int ldv, int64_t v_plane,
                                            void* O, int ldo, int out_mode, int flags, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows,
@@ -1271,10 +1308,11 @@ extern "C" int mmdm_attention_split_ragged(const void* Qp, int ldq, int64_t q_pl
 }
 
 // Vp != nullptr, one plane: V also as bf16 rows [rows][ldvp] -> P.V on the bf16 matrix cores (attn_qkp_kernel<DH, 1, true>);
-// nplanes == 2: Q, K and V (Vp, plane stride v_plane) as the two fp16 planes of the fp32-split mode (attn_qkp_kernel<DH, 2, true, true>)
+// nplanes == 2: Q, K and V (Vp, plane stride v_plane) as the two fp16 planes of the fp32-split mode (attn_qkp_kernel<DH, 2, true, true>);
+// key_valid != nullptr (two planes only): key-padding mask, bytes [mask_rows][Tk] as in mmdm_attention_opts_rag (the MASK instantiation)
 int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, int nplanes, const float* V, int ldv,
                              const void* Vp, int ldvp, int64_t v_plane, void* Ov, int ldo, int out_mode, int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, void* stream,
-                             const mmdm_rag_seq* rg) {
+                             const mmdm_rag_seq* rg, const unsigned char* key_valid, int mask_rows) {
     if (nseq == 0 || Tq == 0) return MMDM_OK;
     if (int rc = mmdm_kernels_init()) return rc;
     if (!Qp || !Kp || (!V && !Vp) || !Ov || nseq < 0 || Tq < 0 || Tk <= 0 || H <= 0 || (nplanes < 1 || nplanes > 3) || (nplanes == 2 && !Vp))
@@ -1293,7 +1331,14 @@ int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const voi
     a.Q = nullptr; a.K = nullptr; a.V = V; a.O = static_cast<float*>(Ov); a.ldq = 0; a.ldk = 0; a.ldv = ldv; a.ldo = ldo;
     a.Qp = static_cast<const __bf16*>(Qp); a.Kp = static_cast<const __bf16*>(Kp); a.q_plane = (size_t)q_plane; a.k_plane = (size_t)k_plane; a.ldqp = ldq; a.ldkp = ldk;
     a.Vp = static_cast<const __bf16*>(Vp); a.ldvp = ldvp; a.v_plane = (size_t)v_plane;
-    a.key_valid = nullptr; a.mask_rows = 1;              // the 16-bit forms take no key mask
+    if (key_valid) {
+        // without the zero key an all-masked first chunk would start the running sums at exp2(-inf - (-inf)) = NaN (mmdm_attention_opts_rag)
+        if (flags) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention with a key mask needs the zero key: MMDM_ATTN_NO_ZERO_KEY / MMDM_ATTN_CAUSAL are not supported with a mask (flags=0x%x)", flags);
+        if (rg) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention with a key mask: ragged batches are not supported (a ragged batch carries its lengths instead)");
+        if (nplanes != 2) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "attention with a key mask: of the 16-bit forms only the two fp16 planes of the fp32-split mode take one (planes=%d)", nplanes);
+        if (mask_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "attention with a key mask: mask_rows=%d must be positive", mask_rows);
+    }
+    a.key_valid = key_valid; a.mask_rows = key_valid ? mask_rows : 1;
     if (Vp && (nplanes == 3 || (reinterpret_cast<uintptr_t>(Vp) & 15) || (ldvp & 7) || ldvp < H * dh || (nplanes == 2 && (v_plane & 7))))
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_attention_planes: 16-bit V needs one (bf16) or two (fp16 split) planes, 16-byte aligned rows / planes and a row stride >= H*dh");
     a.nseq = nseq; a.Tq = Tq; a.Tk = Tk; a.H = H; a.out_bf16 = out_mode; a.flags = flags; a.dh = dh; a.ablate = g_attn_ablate; a.stamps = g_attn_stamps;

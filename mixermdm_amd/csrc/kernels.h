@@ -202,7 +202,7 @@ int mmdm_mean_time_f32_nopk(const float* h, float* out, int nseq, int T, int D, 
 struct mmdm_rag_seq { const int* off; const int* len; int total_rows; int max_len; const int* order = nullptr; int items = 0; };
 int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const void* Kp, int ldk, int64_t k_plane, int nplanes, const float* V, int ldv,
                              const void* Vp, int ldvp, int64_t v_plane, void* O, int ldo, int out_mode, int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, void* stream,
-                             const mmdm_rag_seq* rg = nullptr);
+                             const mmdm_rag_seq* rg = nullptr, const unsigned char* key_valid = nullptr, int mask_rows = 0);
 int mmdm_attention_opts_rag(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* O, int ldo, int out_bf16,
                             int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const mmdm_rag_seq* rg, void* stream,
                             const unsigned char* key_valid = nullptr, int mask_rows = 0);

@@ -646,13 +646,14 @@ const mmdm_rag_seq* rag_seq(const Ctx& c, int nseq, mmdm_rag_seq& tmp) {
     return &tmp;
 }
 
-// attention on 16-bit Q, K and V on the matrix cores: `np` = 1 (bf16 rows) or 2 (the two fp16 planes of the fp32-split mode)
+// attention on 16-bit Q, K and V on the matrix cores: `np` = 1 (bf16 rows) or 2 (the two fp16 planes of the fp32-split mode; with the handle's key mask
+// when one is in force -- the one-plane form never gets here with a mask: run_stack refuses it)
 int attention_p(const Ctx& c, const void* Qp, int ldq, size_t q_plane, const void* Kp, int ldk, size_t k_plane, int np, const void* Vp, int ldvp, size_t v_plane,
                 void* O, int ldo, int out_mode, int nseq, int Tq, int Tk, int H, int dh, int shift) {
     mmdm_rag_seq tmp;
     RC(prof_begin(c, 1, attn_flops(c, nseq, H, Tq, Tk, dh), attn_bytes(c, nseq, H, Tq, Tk, dh)));
     RC(mmdm_attention_planes_ex(Qp, ldq, (int64_t)q_plane, Kp, ldk, (int64_t)k_plane, np, nullptr, 0, Vp, ldvp, (int64_t)v_plane, O, ldo, out_mode, 0, nseq, Tq, Tk, H, dh, shift,
-                                c.st, rag_seq(c, nseq, tmp)));
+                                c.st, rag_seq(c, nseq, tmp), np == 2 ? c.kmask : nullptr, c.kmask_rows));
     return prof_end(c, 1);
 }
 
@@ -704,7 +705,7 @@ int run_stack(const Ctx& c, const StackW& w, float* hbuf, const StackRun& r) {
     // the attention of one block: self (Q, K and V from `q`) or cross (Q from `q`, K and V from `kv`, key sequences shifted by `shift`)
     auto attend = [&](bool cross, int shift) -> int {
         const int ldq = cross ? D : 3 * D, ldkv = cross ? 2 * D : 3 * D;
-        if (c.kmask && w.form != Form::F32) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "key mask: the 16-bit attention forms (precision 1-3) take no mask");
+        if (c.kmask && w.form == Form::BF16) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "key mask: the bf16 attention forms (precision 1 and 3) take no mask");
         if (w.form == Form::F32) {
             const float* k = cross ? S.kv : S.qkv + D;
             return attention_b(c, S.qkv, ldq, k, ldkv, k + D, ldkv, S.att, D, ob, r.nseq, r.T, r.T, w.H, dh, shift);
@@ -2050,8 +2051,8 @@ extern "C" int mmdm_module_forward(mmdm_handle h, int which, const float* x, con
 extern "C" int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, int T) {
     if (!h) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_key_mask: null handle");
     if (!valid_host) { h->mask_rows = 0; h->mask_T = 0; return MMDM_OK; }
-    if (h->cfg.precision != 0)
-        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: precision %d handle -- the 16-bit attention forms take no key mask (precision 0 only)", h->cfg.precision));
+    if (h->cfg.precision != 0 && h->cfg.precision != 2)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: precision %d handle -- the bf16 attention forms take no key mask (precision 0 and 2 only)", h->cfg.precision));
     if (h->cfg.single_only != 2 && h->d1.kind == 1)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: model1_kind = 1 -- the MDM encoder's src_key_padding_mask is not implemented"));
     if (h->cfg.single_only >= 2)

@@ -53,8 +53,9 @@ def key_valid_of(mask):
 
 
 class _KeyMask:
-    """Sets the key mask on a sampler's handle for the duration of one call and clears it afterwards; the cases the library refuses
-    (MMDM_ERR_UNSUPPORTED from mmdm_set_key_mask or from the masked call itself) raise NotImplementedError with the library's message.
+    """Sets the key mask on a sampler's handle for the duration of one call and clears it afterwards (precision "fp32" and "fp32_split"
+    handles); the cases the library refuses -- "bf16" / "bf16_fp8" handles, an MDM denoiser 1, single_only 2 / 3: MMDM_ERR_UNSUPPORTED from
+    mmdm_set_key_mask or from the masked call itself -- raise NotImplementedError with the library's message.
     mask=None: nothing is touched."""
     UNSUPPORTED = 4
 

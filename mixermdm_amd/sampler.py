@@ -257,7 +257,9 @@ class Sampler:
     # ---- key-padding mask ---------------------------------------------------------------------------
     def set_key_mask(self, valid):
         """mmdm_set_key_mask: valid [rows, T] (bool / 0-1; True = the frame exists) or None to clear.  Stays in force for module_forward and
-        begin / run until cleared or replaced; rows = the call's n for module_forward 0, 1, 2, and B for module_forward 4 and the loop."""
+        begin / run until cleared or replaced; rows = the call's n for module_forward 0, 1, 2, and B for module_forward 4 and the loop.
+        precision "fp32" and "fp32_split" handles take a mask (the masked fp32 and two-plane attention kernels); "bf16" / "bf16_fp8", an MDM
+        denoiser 1 and single_only 2 / 3 are refused by the library by name."""
         with torch.cuda.device(self.device):
             if valid is None:
                 check(self.lib.mmdm_set_key_mask(self.h, None, 0, 0), self.h)
