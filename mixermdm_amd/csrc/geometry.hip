@@ -597,35 +597,54 @@ __global__ void gather_rows_kernel(const float* __restrict__ src, const int* __r
 
 }  // namespace
 
+// One launcher per kernel: the rows of the call are an argument (kernels.h mmdm_rows -- uniform, or a ragged batch's row maps), the stateless entry
+// points of include/mmdm.h check their arguments and pass {n, T}.
+// ragged batch: r.n / fr->B groups of fr->rows frame rows (the cond | uncond halves of the CFG-doubled batch)
+int mmdm_mixer_pre(const float* o1, const float* o2, const float* stats, float* out1, float* out2, const mmdm_rows& r, int align, const int* last_frame,
+                   int last_rows, hipStream_t st) {
+    if (r.fr) {
+        const int groups = r.n / r.fr->B, total = groups * r.fr->rows * 2 * MMDM_NJ;
+        hipLaunchKernelGGL(mixer_pre_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, o1, o2, stats, out1, out2, groups, 0, align, *r.fr, (const int*)nullptr, 1);
+        return mmdm_check_launch("mixer_pre_rag");
+    }
+    const int total = r.n * 2 * r.T * MMDM_NJ;
+    hipLaunchKernelGGL(mixer_pre_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, o1, o2, stats, out1, out2, r.n, r.T, align, mmdm_rag{}, last_frame,
+                       last_frame ? last_rows : 1);
+    return mmdm_check_launch("mixer_pre");
+}
+
 extern "C" int mmdm_mixer_pre_f32(const float* o1, const float* o2, const float* stats, float* out1, float* out2,
                                   int n, int T, int align, void* stream) {
     if (n == 0 || T == 0) return MMDM_OK;
     if (!o1 || !o2 || !stats || !out1 || !out2 || n < 0 || T < 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_mixer_pre_f32: bad arguments");
-    const int total = n * 2 * T * MMDM_NJ;
-    hipLaunchKernelGGL(mixer_pre_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), o1, o2, stats, out1, out2, n, T, align, mmdm_rag{},
-                       (const int*)nullptr, 1);
-    return mmdm_check_launch("mixer_pre");
-}
-
-int mmdm_mixer_pre_last(const float* o1, const float* o2, const float* stats, float* out1, float* out2, int n, int T, int align,
-                        const int* last_frame, int last_rows, hipStream_t st) {
-    if (n == 0 || T == 0) return MMDM_OK;
-    if (!o1 || !o2 || !stats || !out1 || !out2 || n < 0 || T < 0 || (last_frame && last_rows <= 0)) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_mixer_pre_masked_f32: bad arguments");
-    const int total = n * 2 * T * MMDM_NJ;
-    hipLaunchKernelGGL(mixer_pre_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, o1, o2, stats, out1, out2, n, T, align, mmdm_rag{}, last_frame, last_frame ? last_rows : 1);
-    return mmdm_check_launch("mixer_pre");
+    return mmdm_mixer_pre(o1, o2, stats, out1, out2, mmdm_rows{n, T}, align, nullptr, 0, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmdm_mixer_pre_masked_f32(const float* o1, const float* o2, const float* stats, float* out1, float* out2,
                                          int n, int T, int align, const int* last_frame, int last_rows, void* stream) {
-    return mmdm_mixer_pre_last(o1, o2, stats, out1, out2, n, T, align, last_frame, last_rows, static_cast<hipStream_t>(stream));
+    if (n == 0 || T == 0) return MMDM_OK;
+    if (!o1 || !o2 || !stats || !out1 || !out2 || n < 0 || T < 0 || (last_frame && last_rows <= 0)) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_mixer_pre_masked_f32: bad arguments");
+    return mmdm_mixer_pre(o1, o2, stats, out1, out2, mmdm_rows{n, T}, align, last_frame, last_rows, static_cast<hipStream_t>(stream));
 }
 
-// ragged batch: `groups` groups of rg.rows frame rows (the cond | uncond halves of the CFG-doubled batch)
-int mmdm_mixer_pre_rag(const float* o1, const float* o2, const float* stats, float* out1, float* out2, int groups, int align, const mmdm_rag& rg, hipStream_t st) {
-    const int total = groups * rg.rows * 2 * MMDM_NJ;
-    hipLaunchKernelGGL(mixer_pre_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, o1, o2, stats, out1, out2, groups, 0, align, rg, (const int*)nullptr, 1);
-    return mmdm_check_launch("mixer_pre_rag");
+// hd != null: the history destinations are read from the device-side descriptor and the slot is chosen on the device (graph replay): see hist_slot().
+// Influence history rows are then [.., 262] for modes 3-4 and [.., 1] for modes 1-2 (the reference's shapes).  Ragged batch: history slots are
+// [2 * fr->rows, C] (padding rows are never written), and only "per frame" vs "per sequence" of Tw matters.
+int mmdm_blend_cfg(const float* out1, const float* out2, const float* w, int mode, int use_force, float force, float cfg_scale, float* model_out,
+                   float* hist_i1, float* hist_i2, float* hist_mix, const mmdm_hist_desc* hd, const int* loop_pos, const mmdm_rows& r, hipStream_t st) {
+    if (mode < 1 || mode > 4) return mmdm_set_error(MMDM_ERR_ARG, "Mixing mode not recognized");   // mixermdm.py:786
+    const bool per_frame = mode == 2 || mode == 4;
+    const int nw = (mode >= 3) ? 23 : 1, nwh = hd && mode < 3 ? 1 : MMDM_NF;
+    if (r.fr) {
+        const size_t total = (size_t)r.fr->rows * NF2;
+        hipLaunchKernelGGL(blend_cfg_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out1, out2, w, per_frame ? 2 : 1, nw, use_force, force,
+                           cfg_scale, model_out, hist_i1, hist_i2, hist_mix, hd, loop_pos, nwh, r.fr->B, 0, *r.fr);
+        return mmdm_check_launch("blend_cfg_rag");
+    }
+    const size_t total = (size_t)r.n * r.T * NF2;
+    hipLaunchKernelGGL(blend_cfg_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out1, out2, w, per_frame ? r.T : 1, nw, use_force, force,
+                       cfg_scale, model_out, hist_i1, hist_i2, hist_mix, hd, loop_pos, nwh, r.n, r.T, mmdm_rag{});
+    return mmdm_check_launch("blend_cfg");
 }
 
 extern "C" int mmdm_blend_cfg_f32(const float* out1, const float* out2, const float* w, int mode, int use_force, float force,
@@ -633,41 +652,8 @@ extern "C" int mmdm_blend_cfg_f32(const float* out1, const float* out2, const fl
                                   int B, int T, void* stream) {
     if (B == 0 || T == 0) return MMDM_OK;
     if (!out1 || !out2 || !w || !model_out || B < 0 || T < 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_blend_cfg_f32: bad arguments");
-    if (mode < 1 || mode > 4) return mmdm_set_error(MMDM_ERR_ARG, "Mixing mode not recognized");   // mixermdm.py:786
-    const int Tw = (mode == 2 || mode == 4) ? T : 1;
-    const int nw = (mode >= 3) ? 23 : 1;
-    const size_t total = (size_t)B * T * NF2;
-    hipLaunchKernelGGL(blend_cfg_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       out1, out2, w, Tw, nw, use_force, force, cfg_scale, model_out, hist_i1, hist_i2, hist_mix,
-                       (const mmdm_hist_desc*)nullptr, (const int*)nullptr, MMDM_NF, B, T, mmdm_rag{});
-    return mmdm_check_launch("blend_cfg");
-}
-
-// Same as mmdm_blend_cfg_f32 with the history destinations read from the device-side descriptor and the slot chosen on the device
-// (graph replay): see hist_slot().  Influence history rows are [.., 262] for modes 3-4 and [.., 1] for modes 1-2 (the reference's shapes).
-int mmdm_blend_cfg_dyn(const float* out1, const float* out2, const float* w, int mode, int use_force, float force, float cfg_scale,
-                       float* model_out, const mmdm_hist_desc* hd, const int* loop_pos, int B, int T, hipStream_t st) {
-    if (mode < 1 || mode > 4) return mmdm_set_error(MMDM_ERR_ARG, "Mixing mode not recognized");
-    const int Tw = (mode == 2 || mode == 4) ? T : 1;
-    const int nw = (mode >= 3) ? 23 : 1;
-    const size_t total = (size_t)B * T * NF2;
-    hipLaunchKernelGGL(blend_cfg_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       out1, out2, w, Tw, nw, use_force, force, cfg_scale, model_out, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                       hd, loop_pos, mode >= 3 ? MMDM_NF : 1, B, T, mmdm_rag{});
-    return mmdm_check_launch("blend_cfg");
-}
-
-// ragged batch: history slots are [2 * rg.rows, C] (padding rows are never written)
-int mmdm_blend_cfg_rag(const float* out1, const float* out2, const float* w, int mode, int use_force, float force, float cfg_scale,
-                       float* model_out, const mmdm_hist_desc* hd, const int* loop_pos, const mmdm_rag& rg, hipStream_t st) {
-    if (mode < 1 || mode > 4) return mmdm_set_error(MMDM_ERR_ARG, "Mixing mode not recognized");
-    const int Tw = (mode == 2 || mode == 4) ? 2 : 1;        // (only "per frame" vs "per sequence" matters to the ragged form)
-    const int nw = (mode >= 3) ? 23 : 1;
-    const size_t total = (size_t)rg.rows * NF2;
-    hipLaunchKernelGGL(blend_cfg_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       out1, out2, w, Tw, nw, use_force, force, cfg_scale, model_out, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                       hd, loop_pos, mode >= 3 ? MMDM_NF : 1, rg.B, 0, rg);
-    return mmdm_check_launch("blend_cfg_rag");
+    return mmdm_blend_cfg(out1, out2, w, mode, use_force, force, cfg_scale, model_out, hist_i1, hist_i2, hist_mix, nullptr, nullptr, mmdm_rows{B, T},
+                          static_cast<hipStream_t>(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -746,51 +732,58 @@ int mmdm_gather_rows(const float* src, const int* idx, float* dst, int n, int D,
     return mmdm_check_launch("gather_rows");
 }
 
+// floor (when the update aligns) + the update, both in the instantiation of the call's rows and noise form; uniform: (B, T), ragged: (rg.B, 0) and the maps
+template <bool RAG>
+static int xstart_ddim_launch(int form, const float* model_out, const float* stats, const float* coef, int S, const int* step_idx, const NoiseArgs& na, float* x,
+                              float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws, int B, int T, int total, int align, const mmdm_rag& rg,
+                              hipStream_t st) {
+    if (align) {
+        hipLaunchKernelGGL(floor_kernel<RAG>, dim3(B * 2), dim3(256), 0, st, model_out, floor_ws, T, rg);
+        if (int rc = mmdm_check_launch(RAG ? "floor_rag" : "floor")) return rc;
+    }
+    const dim3 grid((total + 255) / 256), block(256);
+    if (form == 0)
+        hipLaunchKernelGGL(xstart_ddim_kernel<RAG>, grid, block, 0, st, model_out, stats, coef, S, step_idx, x, x2, pred_xstart, pred_xstart2, floor_ws, B, T, align, rg);
+    else if (form == 1)
+        hipLaunchKernelGGL((xstart_ddim_kernel<RAG, 1, NoiseArgs>), grid, block, 0, st, model_out, stats, coef, S, step_idx, x, x2, pred_xstart, pred_xstart2, floor_ws,
+                           B, T, align, rg, na);
+    else
+        hipLaunchKernelGGL((xstart_ddim_kernel<RAG, 2, NoiseArgs>), grid, block, 0, st, model_out, stats, coef, S, step_idx, x, x2, pred_xstart, pred_xstart2, floor_ws,
+                           B, T, align, rg, na);
+    return mmdm_check_launch(RAG ? "xstart_ddim_rag" : "xstart_ddim");
+}
+
+// the update of both chains: form 0 deterministic, 1 / 2 with step noise (the caller's buffer / the device generator; ragged: the packed buffer / the
+// generator keyed per item).  Ragged batch (fr->B items, fr->rows frame rows incl. padding): same arithmetic per item
+int mmdm_xstart_ddim(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
+                     const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
+                     const mmdm_rows& r, int align, hipStream_t st) {
+    if (form < 0 || form > 2) return mmdm_set_error(MMDM_ERR_ARG, "xstart_ddim: form %d", form);
+    const NoiseArgs na{coef_eta, od, loop_pos};
+    if (r.fr)
+        return xstart_ddim_launch<true>(form, model_out, stats, coef, S, step_idx, na, x, x2, pred_xstart, pred_xstart2, floor_ws, r.fr->B, 0,
+                                        r.fr->rows * 2 * MMDM_NJ, align, *r.fr, st);
+    return xstart_ddim_launch<false>(form, model_out, stats, coef, S, step_idx, na, x, x2, pred_xstart, pred_xstart2, floor_ws, r.n, r.T, r.n * 2 * r.T * MMDM_NJ,
+                                     align, mmdm_rag{}, st);
+}
+
 extern "C" int mmdm_xstart_ddim_f32(const float* model_out, const float* stats, const float* coef, int S, const int* step_idx,
                                     float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
                                     int B, int T, int align, void* stream) {
     if (B == 0 || T == 0) return MMDM_OK;
     if (!model_out || !stats || !coef || !step_idx || !x || !x2 || !floor_ws || S <= 0 || B < 0 || T < 0)
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_xstart_ddim_f32: bad arguments");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (align) {
-        hipLaunchKernelGGL(floor_kernel<false>, dim3(B * 2), dim3(256), 0, st, model_out, floor_ws, T, mmdm_rag{});
-        if (int rc = mmdm_check_launch("floor")) return rc;
-    }
-    const int total = B * 2 * T * MMDM_NJ;
-    hipLaunchKernelGGL(xstart_ddim_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
-                       pred_xstart, pred_xstart2, floor_ws, B, T, align, mmdm_rag{});
-    return mmdm_check_launch("xstart_ddim");
+    return mmdm_xstart_ddim(0, model_out, stats, coef, nullptr, S, step_idx, nullptr, nullptr, x, x2, pred_xstart, pred_xstart2, floor_ws, mmdm_rows{B, T}, align,
+                            static_cast<hipStream_t>(stream));
 }
 
-// the update with step noise (form 1: the caller's buffer, 2: the device generator); uniform batches
-int mmdm_xstart_ddim_noise(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
-                           const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
-                           int B, int T, int align, hipStream_t st) {
-    if (form != 1 && form != 2) return mmdm_set_error(MMDM_ERR_ARG, "xstart_ddim_noise: form %d", form);
-    if (align) {
-        hipLaunchKernelGGL(floor_kernel<false>, dim3(B * 2), dim3(256), 0, st, model_out, floor_ws, T, mmdm_rag{});
-        if (int rc = mmdm_check_launch("floor")) return rc;
+int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rows& r, hipStream_t st) {
+    if (r.fr) {
+        hipLaunchKernelGGL(pin_root_rag_kernel, dim3((r.fr->rows * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, *r.fr);
+        return mmdm_check_launch("pin_root_rag");
     }
-    const int total = B * 2 * T * MMDM_NJ;
-    const NoiseArgs na{coef_eta, od, loop_pos};
-    if (form == 1)
-        hipLaunchKernelGGL((xstart_ddim_kernel<false, 1, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
-                           pred_xstart, pred_xstart2, floor_ws, B, T, align, mmdm_rag{}, na);
-    else
-        hipLaunchKernelGGL((xstart_ddim_kernel<false, 2, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
-                           pred_xstart, pred_xstart2, floor_ws, B, T, align, mmdm_rag{}, na);
-    return mmdm_check_launch("xstart_ddim_noise");
-}
-
-int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, int B, int T, hipStream_t st) {
-    hipLaunchKernelGGL(pin_root_kernel, dim3((B * T * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, B, T);
+    hipLaunchKernelGGL(pin_root_kernel, dim3((r.n * r.T * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, r.n, r.T);
     return mmdm_check_launch("pin_root");
-}
-
-int mmdm_pin_root_rag(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rag& rg, hipStream_t st) {
-    hipLaunchKernelGGL(pin_root_rag_kernel, dim3((rg.rows * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, rg);
-    return mmdm_check_launch("pin_root_rag");
 }
 
 int mmdm_set_item_noise(const unsigned long long* seed_host, const int* row_host, int B, unsigned long long* item_seed, int* item_noise_row, hipStream_t st) {
@@ -818,39 +811,6 @@ extern "C" int mmdm_randn_f32(unsigned long long seed, int loop_pos, int B, int 
     const size_t total = (size_t)B * T * NF2;
     hipLaunchKernelGGL(randn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed, loop_pos, T, total, out);
     return mmdm_check_launch("randn");
-}
-
-// ragged batch (rg.B items, rg.rows frame rows incl. padding): same arithmetic per item
-int mmdm_xstart_ddim_rag(const float* model_out, const float* stats, const float* coef, int S, const int* step_idx,
-                         float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws, int align, const mmdm_rag& rg, hipStream_t st) {
-    if (align) {
-        hipLaunchKernelGGL(floor_kernel<true>, dim3(rg.B * 2), dim3(256), 0, st, model_out, floor_ws, 0, rg);
-        if (int rc = mmdm_check_launch("floor_rag")) return rc;
-    }
-    const int total = rg.rows * 2 * MMDM_NJ;
-    hipLaunchKernelGGL(xstart_ddim_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
-                       pred_xstart, pred_xstart2, floor_ws, rg.B, 0, align, rg);
-    return mmdm_check_launch("xstart_ddim_rag");
-}
-
-// the ragged update with step noise (form 1: the packed buffer, 2: the generator keyed per item)
-int mmdm_xstart_ddim_noise_rag(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
-                               const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
-                               int align, const mmdm_rag& rg, hipStream_t st) {
-    if (form != 1 && form != 2) return mmdm_set_error(MMDM_ERR_ARG, "xstart_ddim_noise_rag: form %d", form);
-    if (align) {
-        hipLaunchKernelGGL(floor_kernel<true>, dim3(rg.B * 2), dim3(256), 0, st, model_out, floor_ws, 0, rg);
-        if (int rc = mmdm_check_launch("floor_rag")) return rc;
-    }
-    const int total = rg.rows * 2 * MMDM_NJ;
-    const NoiseArgs na{coef_eta, od, loop_pos};
-    if (form == 1)
-        hipLaunchKernelGGL((xstart_ddim_kernel<true, 1, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
-                           pred_xstart, pred_xstart2, floor_ws, rg.B, 0, align, rg, na);
-    else
-        hipLaunchKernelGGL((xstart_ddim_kernel<true, 2, NoiseArgs>), dim3((total + 255) / 256), dim3(256), 0, st, model_out, stats, coef, S, step_idx, x, x2,
-                           pred_xstart, pred_xstart2, floor_ws, rg.B, 0, align, rg, na);
-    return mmdm_check_launch("xstart_ddim_noise_rag");
 }
 
 extern "C" int mmdm_cfg_ddim_f32(const float* m, const float* coef, int S, const int* step_idx, float cfg_scale,

@@ -112,14 +112,6 @@ struct mmdm_opts_desc {
     const int* item_noise_row;        // [B] the `b` of every item in the generator's counter; the handle's own array
 };
 int mmdm_set_opts_desc(mmdm_opts_desc* d, const mmdm_opts_desc& v, hipStream_t st);
-int mmdm_xstart_ddim_noise(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
-                           const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
-                           int B, int T, int align, hipStream_t st);
-int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, int B, int T, hipStream_t st);
-int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st);
-int mmdm_hist_copy(const float* src, const mmdm_hist_desc* hd, int which, size_t count, const int* loop_pos, hipStream_t st);
-int mmdm_blend_cfg_dyn(const float* out1, const float* out2, const float* w, int mode, int use_force, float force, float cfg_scale,
-                       float* model_out, const mmdm_hist_desc* hd, const int* loop_pos, int B, int T, hipStream_t st);
 // A RAGGED batch as the geometry kernels see it (device arrays written by mmdm_rag_setup; one group = the B items' frames back to back, padded to `rows`)
 constexpr int MMDM_RAG_MAX_ITEMS = 256;      // item lengths travel to the device by value (kernel argument)
 struct mmdm_rag {
@@ -129,29 +121,37 @@ struct mmdm_rag {
     const int* item_len;   // [B]
     int B, rows;           // items; group stride in frame rows (sum of lengths rounded up to the handle's row bucket)
 };
+// The rows one launch of a row or geometry kernel covers: `n` sequences (or items) of T frames each, or -- a RAGGED batch -- n sequences in groups of fr->B
+// whose frames lie back to back (mmdm_rag).  Built in one place from the call's geometry (mmdm.hip rows()); the stateless entry points of
+// include/mmdm.h pass {n, T}.
+struct mmdm_rows {
+    int n = 0, T = 0;                                       // ragged: T is unused, n / fr->B groups
+    const mmdm_rag* fr = nullptr;                           // ragged: the frame rows of a group
+    const mmdm_rag* tk = nullptr;                           // ragged, the MDM pack / unpack pair: the token rows of a group
+    const int *seq_off = nullptr, *seq_len = nullptr;       // ragged, the time mean: first row and length of every sequence [n]
+};
+// One internal launcher per geometry kernel (geometry.hip); no argument checks: those are the stateless entry points'.
+// last_frame (uniform rows only; may be null): the alignment's end frame per sequence, [last_rows] DEVICE ints, batch row b reads entry b % last_rows
+int mmdm_mixer_pre(const float* o1, const float* o2, const float* stats, float* out1, float* out2, const mmdm_rows& r, int align, const int* last_frame,
+                   int last_rows, hipStream_t st);
+// r = one half of the CFG-doubled batch.  History: hd / loop_pos (the device-side descriptor and slot: the handles), or hd == null and the three explicit
+// destinations (slot 0: mmdm_blend_cfg_f32)
+int mmdm_blend_cfg(const float* out1, const float* out2, const float* w, int mode, int use_force, float force, float cfg_scale, float* model_out,
+                   float* hist_i1, float* hist_i2, float* hist_mix, const mmdm_hist_desc* hd, const int* loop_pos, const mmdm_rows& r, hipStream_t st);
+// form 0: the deterministic update (coef_eta / loop_pos / od unused); 1 / 2: + step noise from the call's buffer / the device generator (ragged: the packed
+// buffer / the generator keyed per item).  r = the B items of the call.
+int mmdm_xstart_ddim(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
+                     const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
+                     const mmdm_rows& r, int align, hipStream_t st);
+int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rows& r, hipStream_t st);
+int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st);
+int mmdm_hist_copy(const float* src, const mmdm_hist_desc* hd, int which, size_t count, const int* loop_pos, hipStream_t st);
 int mmdm_rag_setup(const int* lens_host, int B, int rows, int groups, int* item_off, int* item_len, int* row_item, int* row_pos, int* row_seq,
                    int* seq_off, int* seq_len, int* item_order, hipStream_t st);
-int mmdm_mixer_pre_rag(const float* o1, const float* o2, const float* stats, float* out1, float* out2, int groups, int align, const mmdm_rag& rg, hipStream_t st);
-int mmdm_blend_cfg_rag(const float* out1, const float* out2, const float* w, int mode, int use_force, float force, float cfg_scale,
-                       float* model_out, const mmdm_hist_desc* hd, const int* loop_pos, const mmdm_rag& rg, hipStream_t st);
-int mmdm_xstart_ddim_rag(const float* model_out, const float* stats, const float* coef, int S, const int* step_idx,
-                         float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws, int align, const mmdm_rag& rg, hipStream_t st);
-// the ragged update with step noise (form 1: the packed buffer, 2: the generator keyed per item) and the ragged root pin (geometry.hip)
-int mmdm_xstart_ddim_noise_rag(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
-                               const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
-                               int align, const mmdm_rag& rg, hipStream_t st);
-int mmdm_pin_root_rag(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rag& rg, hipStream_t st);
 // per-item generator identity of a ragged call: B host values each, passed by value like the lengths (row_host may be null: zeros)
 int mmdm_set_item_noise(const unsigned long long* seed_host, const int* row_host, int B, unsigned long long* item_seed, int* item_noise_row, hipStream_t st);
 int mmdm_linear_f32_ex(const float* A, int lda, const float* W, int ldw, int Kw, const float* bias, float* C, int ldc,
                        int M, int N, int K, int epilogue, const float* extra, int ld_extra, int period, void* stream);
-int mmdm_mdm_pack(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
-                  int nseq, int T, int D, hipStream_t st);
-int mmdm_mdm_unpack(const float* src, float* dst, int nseq, int T, int D, hipStream_t st);
-// ragged forms (rowops.hip): frame groups `fr` <-> token groups `tk` of `groups` groups, `gpp` groups per person (the CFG halves)
-int mmdm_mdm_pack_rag(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
-                      int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
-int mmdm_mdm_unpack_rag(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
 int mmdm_repack_pose(const float* src, int ld_src, float* dst, int npers, int rows, int ldp, int split, hipStream_t st);
 int mmdm_linear_split_ex(const void* A, int lda, int64_t a_plane, const void* W, int ldw, int64_t w_plane, const float* bias, void* C, int ldc,
                          int64_t c_plane, int out_split, int M, int N, int K, int epilogue, const float* extra, int ld_extra, int period,
@@ -161,39 +161,29 @@ int mmdm_linear_bf16_ex(const void* A, int lda, const void* W, int ldw, const fl
 int mmdm_linear_fp8_ex(const void* A, int lda, const float* a_scale, const void* W, int ldw, const float* w_scale, const float* bias, void* C, int ldc,
                        int out_mode, int M, int N, int K, int epilogue, const float* extra, int ld_extra, int period, void* bf16_copy, int ld2, int copy_cols,
                        float a_const, float out_scale, void* stream);
-int mmdm_adaln_any(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_mode, float* row_scale, int nseq, int T, int D, void* stream,
-                   const int* row_seq = nullptr, int rows_rag = 0);
-int mmdm_mean_time_rag(const float* h, float* out, int nseq, const int* seq_off, const int* seq_len, int D, hipStream_t st);
-// rowops.hip's second build (rowops_nopk.o: no packed-fp32 VALU instructions; mixermdm_amd/build.py), taken by precision 1-3 handles through mmdm.hip's ROWOP
-int mmdm_adaln_any_nopk(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_mode, float* row_scale, int nseq, int T, int D, void* stream,
-                        const int* row_seq = nullptr, int rows_rag = 0);
-int mmdm_mean_time_rag_nopk(const float* h, float* out, int nseq, const int* seq_off, const int* seq_len, int D, hipStream_t st);
-int mmdm_mdm_pack_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
-                       int nseq, int T, int D, hipStream_t st);
-int mmdm_mdm_unpack_nopk(const float* src, float* dst, int nseq, int T, int D, hipStream_t st);
-int mmdm_mdm_pack_rag_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
-                           int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
-int mmdm_mdm_unpack_rag_nopk(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
-// Row kernels of the fp32-split post-norm encoder (MDMDenoiser, precision 2; rowops.hip, both builds): LayerNorm and the sequence assembly write the fp32
-// rows (residual) and their two fp16 planes (GEMM operand: planes [2][rows][D], plane stride in elements) in one pass
-int mmdm_layernorm_planes(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps, hipStream_t st);
-int mmdm_layernorm_planes_nopk(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps, hipStream_t st);
-int mmdm_mdm_pack_planes(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
-                         int64_t plane_stride, int nseq, int T, int D, hipStream_t st);
-int mmdm_mdm_pack_planes_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
-                              int64_t plane_stride, int nseq, int T, int D, hipStream_t st);
-int mmdm_mdm_pack_rag_planes(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
-                             int64_t plane_stride, int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
-int mmdm_mdm_pack_rag_planes_nopk(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
-                                  int64_t plane_stride, int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st);
-// silu(time_tab[*step_idx] + txt) as the two fp16 planes of the fp32-split GEMM's A operand (rowops.hip)
-int mmdm_cond_silu_planes(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st);
-int mmdm_cond_silu_planes_nopk(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st);
-extern "C" {
-int mmdm_layernorm_f32_nopk(const float* x, const float* gamma, const float* beta, float* out, int rows, int D, float eps, void* stream);
-int mmdm_cond_silu_f32_nopk(const float* time_tab, const int* step_idx, const float* txt, float* out, int rows, int D, void* stream);
-int mmdm_mean_time_f32_nopk(const float* h, float* out, int nseq, int T, int D, void* stream);
-}
+// The row operations a handle's step uses (rowops.hip), one table per build of that file: mmdm_rowops_tab is rowops.o as it stands (precision 0 handles and
+// the stateless entry points), mmdm_rowops_tab_nopk is rowops_nopk.o -- the same kernels without packed-fp32 VALU instructions (mixermdm_amd/build.py),
+// which precision 1-3 handles take.  A caller picks the table once (mmdm.hip Ctx::ro) and calls through it.
+struct mmdm_rowops {
+    // row_seq != nullptr: ragged batch -- `rows_rag` rows in all, row r belongs to sequence row_seq[r] (device array); nseq / T are then unused
+    int (*adaln)(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_mode, float* row_scale, int nseq, int T, int D, void* stream,
+                 const int* row_seq, int rows_rag);
+    int (*layernorm)(const float* x, const float* gamma, const float* beta, float* out, int rows, int D, float eps, void* stream);
+    // the fp32-split post-norm encoder (MDMDenoiser, precision 2): the fp32 rows (residual) and their two fp16 planes (GEMM operand: planes [2][rows][D],
+    // plane stride in elements) in one pass
+    int (*layernorm_planes)(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
+                            hipStream_t st);
+    int (*cond_silu)(const float* time_tab, const int* step_idx, const float* txt, float* out, int rows, int D, void* stream);
+    // silu(time_tab[*step_idx] + txt) as the two fp16 planes of the fp32-split GEMM's A operand
+    int (*cond_silu_planes)(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st);
+    int (*mean_time)(const float* h, float* out, const mmdm_rows& r, int D, hipStream_t st);
+    // MDMDenoiser's sequence assembly and its inverse: frame rows <-> token rows (ragged: r.fr <-> r.tk, `gpp` groups per person -- the CFG halves);
+    // planes != null: the assembled rows' two fp16 planes as a second output
+    int (*mdm_pack)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                    int64_t plane_stride, const mmdm_rows& r, int gpp, int D, hipStream_t st);
+    int (*mdm_unpack)(const float* src, float* dst, const mmdm_rows& r, int D, hipStream_t st);
+};
+extern const mmdm_rowops mmdm_rowops_tab, mmdm_rowops_tab_nopk;
 // Sequences of a RAGGED batch as the attention kernels see them (device arrays: one captured graph serves every batch of the same row bucket):
 // sequence s owns rows [off[s], off[s] + len[s]) of Q / K / V / O; total_rows = rows of O (plane stride of a split output); max_len sizes the grid.
 // order / items (optional): the batch's B items sorted by length, longest first (written by mmdm_rag_setup); the nseq = k x B sequences of a launch are then
@@ -206,6 +196,3 @@ int mmdm_attention_planes_ex(const void* Qp, int ldq, int64_t q_plane, const voi
 int mmdm_attention_opts_rag(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* O, int ldo, int out_bf16,
                             int flags, int nseq, int Tq, int Tk, int H, int dh, int kv_seq_shift, const mmdm_rag_seq* rg, void* stream,
                             const unsigned char* key_valid = nullptr, int mask_rows = 0);
-// mmdm_mixer_pre_f32 with the alignment's end frame per sequence (geometry.hip): last_frame [last_rows] DEVICE ints, batch row b reads entry b % last_rows
-int mmdm_mixer_pre_last(const float* o1, const float* o2, const float* stats, float* out1, float* out2, int n, int T, int align,
-                        const int* last_frame, int last_rows, hipStream_t st);

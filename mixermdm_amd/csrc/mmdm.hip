@@ -61,8 +61,7 @@ static std::shared_mutex g_graph_mu;
 // kernels it takes is not isolated (LAB_NOTES.md; tools/canary.hip, tools/overlap_bisect.py).  The rule is therefore by construction
 // (mixermdm_amd/build.py): geometry.hip is built without packed-fp32 instructions for every handle, and precision 1-3 handles take the
 // row kernels (AdaLN, LayerNorm, cond SiLU, time mean, MDM pack / unpack) of rowops_nopk.o -- the second build of rowops.hip, without them --
-// through ROWOP below; tests/test_gpu_ragged.py keeps full-size handles of every precision pair side by side bit-exact.
-#define ROWOP(c, fn, ...) (((c).h && (c).h->cfg.precision != 0) ? fn##_nopk(__VA_ARGS__) : fn(__VA_ARGS__))
+// through the table their context picks (Ctx::ro below); tests/test_gpu_ragged.py keeps full-size handles of every precision pair side by side bit-exact.
 // MMDM_SERIALIZE_HANDLES=1 (read once, by the first mmdm_create): every sampling call (mmdm_run) waits on the device for the previous
 // sampling call of ANY handle of the process -- one process-wide event, no host synchronisation -- so that overlap between handles can be
 // ruled out in the field as the cause of a wrong motion.  Off by default.
@@ -216,6 +215,25 @@ struct Prof {
     double bytes[NCLS] = {0, 0, 0, 0};           // algorithmic bytes (operands read once + result written once)
 };
 
+// What the nodes of a captured step graph bake in, field by field: two calls with equal keys launch the same kernels with the same arguments.  Everything
+// else -- history destinations, schedule tables, conditioning, the step index, a ragged batch's lengths, the VALUES of the call's options and mask -- is
+// device data behind fixed addresses, so the eval caller's alternating (B, T) requests (src/evaluation/datasets.py:101-122, 438) replay cached graphs.
+struct GraphKey {
+    int B;          // items of the call: every grid, row count and GEMM shape
+    int T;          // uniform: frames per item (row counts, attention tiles).  Ragged: query tiles of the longest item -- the attention grids only
+    int S;          // steps of the schedule: an argument of the update kernels (the stride of the coefficient tables)
+    int rows;       // ragged: group stride in frame rows (row counts, GEMM shapes; the lengths inside it are device data); 0 = a uniform call
+    int masked;     // a key mask is in force: the attention and alignment nodes hold the mask buffers' addresses instead of null
+    int trows;      // ragged with MDM as denoiser 1: group stride of its encoder's token rows; 0 otherwise
+    int tT;         // ... and query tiles of the longest token sequence (T + 1 rows: 64 frames are one tile of frames and two of tokens); 0 otherwise
+    int noise;      // noise form 0 / 1 / 2 of the call: which instantiation of the update kernel ends the step
+    int pinned;     // x_start given: pin_root_kernel is the step's first node
+    bool operator==(const GraphKey& o) const {
+        return B == o.B && T == o.T && S == o.S && rows == o.rows && masked == o.masked && trows == o.trows && tT == o.tT && noise == o.noise && pinned == o.pinned;
+    }
+};
+struct GraphEntry { GraphKey key; hipGraphExec_t exec; uint64_t used; hipEvent_t done; };      // done: recorded behind the entry's last replay
+
 }  // namespace
 
 // Device memory of a handle's WEIGHTS (fp32 parameters, packed AdaLN matrices, the low-precision twins made by mmdm_prepare, normaliser
@@ -304,13 +322,7 @@ struct mmdm_handle_s {
     int mask_rows = 0, mask_T = 0;          // 0 rows: no mask set
     hipStream_t call_stream = nullptr;      // stream of the last mmdm_begin: mmdm_set_history orders its descriptor update on it
 
-    // Captured step graphs, least-recently-used cache keyed by everything a captured node bakes in: (B, T, S).  History
-    // destinations, schedule tables, conditioning and the step index are device-side data, not node arguments, so the eval
-    // caller's alternating (B, T) requests (src/evaluation/datasets.py:101-122, 438) replay cached graphs instead of re-capturing.
-    // (ragged calls: T = query tiles of the longest item, rows = the group stride; uniform calls: rows = 0.  Ragged calls with MDM as denoiser 1: trows =
-    // the token stride, tT = query tiles of the longest token sequence -- 64 frames are one tile of frames and two of tokens; 0 otherwise)
-    // (noise / pinned: the call's noise form and whether it pins the roots -- other kernels, so other entries; the option VALUES are device data)
-    struct GraphEntry { int B, T, S, rows; hipGraphExec_t exec; uint64_t used; hipEvent_t done; int masked; int trows, tT; int noise, pinned; };      // done: recorded behind the entry's last replay
+    // captured step graphs: a least-recently-used cache, one entry per GraphKey
     std::vector<GraphEntry> graphs;
     size_t graph_cap = 8;
     uint64_t graph_clock = 0;
@@ -534,8 +546,19 @@ struct Ctx {
     const unsigned char* kmask = nullptr;
     const int* klast = nullptr;
     int kmask_rows = 0;
+    // the row operations of this context, chosen once: precision 0 handles and the stateless composites take rowops.o, every other handle the build without
+    // packed-fp32 instructions (the comment above g_serialize_handles has the reason)
+    const mmdm_rowops& ro;
+    Ctx(mmdm_handle h_, hipStream_t st_, const Scratch* s_, const Geom* g_ = nullptr)
+        : h(h_), st(st_), s(s_), g(g_), ro(h_ && h_->cfg.precision != 0 ? mmdm_rowops_tab_nopk : mmdm_rowops_tab) {}
+    Ctx on(hipStream_t st2, const Scratch* s2) const { Ctx c = *this; c.st = st2; c.s = s2; return c; }      // the same call on another stream and scratch set
     bool rag() const { return g && g->rag; }
     size_t rows_of(int nseq, int T) const { return g ? g->rows_of(nseq) : (size_t)nseq * T; }
+    // `nseq` sequences of the call as a row or geometry launcher takes them (kernels.h mmdm_rows): uniform (nseq, T), or the ragged call's row maps
+    mmdm_rows rows(int nseq, int T) const {
+        if (!rag()) return mmdm_rows{nseq, T};
+        return mmdm_rows{nseq, T, &g->rg, g->tk.rows ? &g->tk : nullptr, g->seq_off, g->seq_len};
+    }
 };
 
 // the row-split rule of the fp32 GEMM dispatch is thread-local state: set for the duration of one step / module forward, then restored
@@ -579,12 +602,18 @@ int linear(const Ctx& c, const float* A, int lda, const float* W, int ldw, const
     return prof_end(c, cls);
 }
 
+// profile accounting of one self-attention launch WITHOUT the zero key (nn.TransformerEncoderLayer): 4 dh T^2 per (sequence, head).  tokens: the launch walks
+// the token sequences of a ragged MDM call -- the sum of their squared lengths and of their lengths (one token in front of every item's frames) come from its geometry
+int prof_begin_plain_attn(const Ctx& c, int nseq, int T, int H, int dh, bool tokens) {
+    if (!tokens) return prof_begin(c, 1, 4.0 * nseq * H * (double)T * T * dh, 4.0 * nseq * H * dh * 4.0 * T);
+    const Geom& g = *c.g;
+    return prof_begin(c, 1, 4.0 * (nseq / g.B) * H * dh * g.tok_tt, 4.0 * (nseq / g.B) * H * dh * 4.0 * ((double)g.real_rows + g.B));
+}
+
 // plain self-attention of nn.TransformerEncoderLayer (no zero key)
-// rg: the sequences of a ragged launch (the token sequences of a ragged MDM call; T = the longest); `tt` = sum of their squared lengths, `real` = of their lengths
-int attention_plain(const Ctx& c, const float* qkv, int ld, float* O, int ldo, int nseq, int T, int H, int dh, int flags, const mmdm_rag_seq* rg = nullptr,
-                    double tt = 0, double real = 0) {
-    if (rg) RC(prof_begin(c, 1, 4.0 * (nseq / rg->items) * H * dh * tt, 4.0 * (nseq / rg->items) * H * dh * 4.0 * real));
-    else RC(prof_begin(c, 1, 4.0 * nseq * H * (double)T * T * dh, 4.0 * nseq * H * dh * 4.0 * T));
+// rg: the sequences of a ragged launch (the token sequences of a ragged MDM call; T = the longest)
+int attention_plain(const Ctx& c, const float* qkv, int ld, float* O, int ldo, int nseq, int T, int H, int dh, int flags, const mmdm_rag_seq* rg = nullptr) {
+    RC(prof_begin_plain_attn(c, nseq, T, H, dh, rg != nullptr));
     RC(mmdm_attention_opts_rag(qkv, ld, qkv + H * dh, ld, qkv + 2 * H * dh, ld, O, ldo, 0, flags, nseq, T, T, H, dh, 0, rg, c.st));
     return prof_end(c, 1);
 }
@@ -696,7 +725,7 @@ int run_stack(const Ctx& c, const StackW& w, float* hbuf, const StackRun& r) {
     };
     // AdaLN into the stack GEMMs' operand format: fp32 / bf16 / two fp16 planes, or fp8 + per-row scales
     auto norm = [&](const float* src, const float* ssp, int rows) -> int {
-        return ROWOP(c, mmdm_adaln_any, src, ssp, r.ss_ld, rows, S.xn, f8 ? 3 : ob, f8 ? S.xs : nullptr, r.nseq, r.T, D, c.st, row_seq, R);
+        return c.ro.adaln(src, ssp, r.ss_ld, rows, S.xn, f8 ? 3 : ob, f8 ? S.xs : nullptr, r.nseq, r.T, D, c.st, row_seq, R);
     };
     // where the projections go: self Q|K|V [R][3D] and cross-attention Q [R][D] in `q`, cross-attention K|V [R][2D] in `kv` -- the bf16 buffers of
     // Form::BF16, else the fp32 buffers (holding the two fp16 planes in Form::SPLIT)
@@ -763,10 +792,10 @@ int cond_vectors(const Ctx& c, const ModuleW& m, const float* txt, float* se, fl
     const int N = ss_ld_of(m);
     if (w.ada_s) {       // low-precision handles: `se` holds the two fp16 planes of silu(.) (as many bytes), the projection runs on the fp32-split kernel
         const size_t pa = (size_t)rows * w.D;
-        RC(mmdm_cond_silu_planes_nopk(m.time_tab, c.h->d_step, txt, reinterpret_cast<_Float16*>(se), pa, rows, w.D, c.st));
+        RC(c.ro.cond_silu_planes(m.time_tab, c.h->d_step, txt, reinterpret_cast<_Float16*>(se), pa, rows, w.D, c.st));
         return linear_s(c, se, w.D, pa, w.ada_s, c.h->no_pack ? w.D : 0, (size_t)N * w.D, w.ada_b, ss, N, 0, 0, rows, N, w.D, MMDM_EPI_BIAS, nullptr, 0);
     }
-    RC(ROWOP(c, mmdm_cond_silu_f32, m.time_tab, c.h->d_step, txt, se, rows, w.D, c.st));
+    RC(c.ro.cond_silu(m.time_tab, c.h->d_step, txt, se, rows, w.D, c.st));
     return linear(c, se, w.D, w.ada_w, w.D, w.ada_b, ss, N, rows, N, w.D);
 }
 
@@ -823,26 +852,26 @@ int run_denoiser(const Ctx& c, const ModuleW& m, bool interaction, const float* 
 // rg (a ragged MDM call): the nseq sequences are rg's, in groups of rg->total_rows rows in all (padding rows included) -- the GEMMs and LayerNorm run on
 // every row, the attention walks the sequences; T = the longest.
 int encoder_layer(const Ctx& c, float* x, const EncLayerW& w, int nseq, int T, int D, int H, int F, bool norm_first, int act_epi, bool causal,
-                  float eps, float* qkv, float* att, float* tmp, float* f1, const mmdm_rag_seq* rg = nullptr, double rg_tt = 0, double rg_real = 0) {
+                  float eps, float* qkv, float* att, float* tmp, float* f1, const mmdm_rag_seq* rg = nullptr) {
     const int R = rg ? rg->total_rows : nseq * T, dh = D / H;
     const int flags = MMDM_ATTN_NO_ZERO_KEY | (causal ? MMDM_ATTN_CAUSAL : 0);
     if (norm_first) {
         if (rg) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "encoder layer: ragged batches cover the post-norm form only");
-        RC(ROWOP(c, mmdm_layernorm_f32, x, w.n1_g, w.n1_b, tmp, R, D, eps, c.st));
+        RC(c.ro.layernorm(x, w.n1_g, w.n1_b, tmp, R, D, eps, c.st));
         RC(linear(c, tmp, D, w.in_w, D, w.in_b, qkv, 3 * D, R, 3 * D, D));
         RC(attention_plain(c, qkv, 3 * D, att, D, nseq, T, H, dh, flags));
         RC(linear(c, att, D, w.out_w, D, w.out_b, x, D, R, D, D, MMDM_EPI_BIAS_RESID, x, D));
-        RC(ROWOP(c, mmdm_layernorm_f32, x, w.n2_g, w.n2_b, tmp, R, D, eps, c.st));
+        RC(c.ro.layernorm(x, w.n2_g, w.n2_b, tmp, R, D, eps, c.st));
         RC(linear(c, tmp, D, w.l1_w, D, w.l1_b, f1, F, R, F, D, act_epi));
         return linear(c, f1, F, w.l2_w, F, w.l2_b, x, D, R, D, F, MMDM_EPI_BIAS_RESID, x, D);
     }
     RC(linear(c, x, D, w.in_w, D, w.in_b, qkv, 3 * D, R, 3 * D, D));
-    RC(attention_plain(c, qkv, 3 * D, att, D, nseq, T, H, dh, flags, rg, rg_tt, rg_real));
+    RC(attention_plain(c, qkv, 3 * D, att, D, nseq, T, H, dh, flags, rg));
     RC(linear(c, att, D, w.out_w, D, w.out_b, tmp, D, R, D, D, MMDM_EPI_BIAS_RESID, x, D));
-    RC(ROWOP(c, mmdm_layernorm_f32, tmp, w.n1_g, w.n1_b, x, R, D, eps, c.st));
+    RC(c.ro.layernorm(tmp, w.n1_g, w.n1_b, x, R, D, eps, c.st));
     RC(linear(c, x, D, w.l1_w, D, w.l1_b, f1, F, R, F, D, act_epi));
     RC(linear(c, f1, F, w.l2_w, F, w.l2_b, tmp, D, R, D, F, MMDM_EPI_BIAS_RESID, x, D));
-    return ROWOP(c, mmdm_layernorm_f32, tmp, w.n2_g, w.n2_b, x, R, D, eps, c.st);
+    return c.ro.layernorm(tmp, w.n2_g, w.n2_b, x, R, D, eps, c.st);
 }
 
 // The post-norm layer on SPLIT operands (precision 2; MDMDenoiser): fp32 results from the fp16 matrix cores.  A post-norm layer uses its
@@ -853,24 +882,23 @@ int encoder_layer(const Ctx& c, float* x, const EncLayerW& w, int nseq, int T, i
 //   f1    = planes(gelu(xs W_1^T + b))                  tmp = f1 W_2^T + b + x;  x, xs = LN2(tmp)   (last layer: x only -- nothing reads its planes)
 // Weights: the layer's fp16-plane twins (EncLayerW::*_s), in fragment order when `packed`.  rg as in encoder_layer.
 int encoder_layer_split(const Ctx& c, float* x, void* xs, const EncLayerW& w, bool packed, int nseq, int T, int D, int H, int F, float eps, void* qkv, void* att,
-                        float* tmp, void* f1, bool last, const mmdm_rag_seq* rg = nullptr, double rg_tt = 0, double rg_real = 0) {
+                        float* tmp, void* f1, bool last, const mmdm_rag_seq* rg = nullptr) {
     const int R = rg ? rg->total_rows : nseq * T, dh = D / H;
     const size_t RD = (size_t)R * D;
     RC(linear_s(c, xs, D, RD, w.in_s, packed ? 0 : D, (size_t)3 * D * D, w.in_b, qkv, 3 * D, (size_t)R * 3 * D, 1, R, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0));
     {
         const uint16_t* q = static_cast<const uint16_t*>(qkv);
-        if (rg) RC(prof_begin(c, 1, 4.0 * (nseq / rg->items) * H * dh * rg_tt, 4.0 * (nseq / rg->items) * H * dh * 4.0 * rg_real));
-        else RC(prof_begin(c, 1, 4.0 * nseq * H * (double)T * T * dh, 4.0 * nseq * H * dh * 4.0 * T));
+        RC(prof_begin_plain_attn(c, nseq, T, H, dh, rg != nullptr));
         RC(mmdm_attention_planes_ex(q, 3 * D, (int64_t)R * 3 * D, q + D, 3 * D, (int64_t)R * 3 * D, 2, nullptr, 0, q + 2 * D, 3 * D, (int64_t)R * 3 * D, att, D, 2,
                                     MMDM_ATTN_NO_ZERO_KEY, nseq, T, T, H, dh, 0, c.st, rg));
         RC(prof_end(c, 1));
     }
     RC(linear_s(c, att, D, RD, w.out_s, packed ? 0 : D, (size_t)D * D, w.out_b, tmp, D, 0, 0, R, D, D, MMDM_EPI_BIAS_RESID, x, D));
-    RC(ROWOP(c, mmdm_layernorm_planes, tmp, w.n1_g, w.n1_b, x, xs, (int64_t)RD, R, D, eps, c.st));
+    RC(c.ro.layernorm_planes(tmp, w.n1_g, w.n1_b, x, xs, (int64_t)RD, R, D, eps, c.st));
     RC(linear_s(c, xs, D, RD, w.l1_s, packed ? 0 : D, (size_t)F * D, w.l1_b, f1, F, (size_t)R * F, 1, R, F, D, MMDM_EPI_BIAS_GELU, nullptr, 0));
     RC(linear_s(c, f1, F, (size_t)R * F, w.l2_s, packed ? 0 : F, (size_t)D * F, w.l2_b, tmp, D, 0, 0, R, D, F, MMDM_EPI_BIAS_RESID, x, D));
-    if (last) return ROWOP(c, mmdm_layernorm_f32, tmp, w.n2_g, w.n2_b, x, R, D, eps, c.st);
-    return ROWOP(c, mmdm_layernorm_planes, tmp, w.n2_g, w.n2_b, x, xs, (int64_t)RD, R, D, eps, c.st);
+    if (last) return c.ro.layernorm(tmp, w.n2_g, w.n2_b, x, R, D, eps, c.st);
+    return c.ro.layernorm_planes(tmp, w.n2_g, w.n2_b, x, xs, (int64_t)RD, R, D, eps, c.st);
 }
 
 // MDMDenoiser.forward (mdm.py:273-298) on the CFG-doubled batch: `cond` rows are [n, ldc] with person p's latent-sized slice at
@@ -885,51 +913,31 @@ int run_denoiser_mdm(const Ctx& c, const ModuleW& m, const float* x, int xb, int
     for (int p = 0; p < npers; ++p)
         for (int rep = 0; rep < n / xb; ++rep)
             RC(embed(c, m, S.xp, p, S.att + c.rows_of(p * n + rep * xb, T) * D, xb, T, 1));
+    // The encoder runs on TOKEN rows: uniform nseq sequences of T + 1 rows; ragged nseq / B token groups, walked by the attention through `tseq`.
     // precision 2: the split operand form of the encoder (encoder_layer_split).  Buffers of the handle's scratch set: x = S.h (fp32), its planes in S.xn,
     // Q|K|V planes in S.qkv, attention planes in S.att (free once the assembly has read the pose embeddings), fp32 sub-layer output in S.kv, GELU planes in S.f1
-    const bool split = c.h->cfg.precision == 2;
-    const int Lm = m.st.L;
-    if (split && c.rag()) {
-        const Geom& g = *c.g;
-        if (!g.tk.rows) return mmdm_set_error(MMDM_ERR_STATE, "ragged MDM denoiser: the call has no token maps");
-        const int groups = nseq / g.B;
-        const size_t RD = (size_t)groups * g.tk.rows * D;
-        const mmdm_rag_seq tseq{g.tok_seq_off, g.tok_seq_len, groups * g.tk.rows, T + 1, g.item_order, g.B};
-        RC(ROWOP(c, mmdm_mdm_pack_rag_planes, S.att, cond, ldc, m.time_tab, c.h->d_step, m.pe, S.h, S.xn, (int64_t)RD, groups, n / g.B, D, g.rg, g.tk, c.st));
-        // the attention writes the rows of the sequences only: the padding token rows of its output planes are zeroed once (S.att held fp32 embeddings)
-        HIPCHK(hipMemsetAsync(S.att, 0, RD * 2 * sizeof(uint16_t), c.st));
-        for (int l = 0; l < Lm; ++l)
-            RC(encoder_layer_split(c, S.h, S.xn, m.enc[l], m.st.w_packed, nseq, T + 1, D, m.st.H, m.st.F, 1e-5f, S.qkv, S.att, S.kv, S.f1, l + 1 == Lm, &tseq, g.tok_tt,
-                                   (double)g.real_rows + g.B));
-        RC(ROWOP(c, mmdm_mdm_unpack_rag, S.h, S.att, groups, D, g.rg, g.tk, c.st));
-    } else if (split) {
-        const size_t RD = (size_t)nseq * (T + 1) * D;
+    const bool split = c.h->cfg.precision == 2, rag = c.rag();
+    if (rag && !c.g->tk.rows) return mmdm_set_error(MMDM_ERR_STATE, "ragged MDM denoiser: the call has no token maps");
+    const size_t RD = (rag ? (size_t)(nseq / c.g->B) * c.g->tk.rows : (size_t)nseq * (T + 1)) * D;
+    const mmdm_rag_seq tseq_rag = rag ? mmdm_rag_seq{c.g->tok_seq_off, c.g->tok_seq_len, (nseq / c.g->B) * c.g->tk.rows, T + 1, c.g->item_order, c.g->B} : mmdm_rag_seq{};
+    const mmdm_rag_seq* const tseq = rag ? &tseq_rag : nullptr;
+    uint16_t* const planes = split ? reinterpret_cast<uint16_t*>(S.xn) : nullptr;       // layer 0's operand, written by the assembly
+    // assemble the tokens: one pass over the groups of a ragged call, one per person otherwise (person p's cond slice sits at column p * D)
+    if (rag) RC(c.ro.mdm_pack(S.att, cond, ldc, m.time_tab, c.h->d_step, m.pe, S.h, planes, (int64_t)RD, c.rows(nseq, T), n / c.g->B, D, c.st));
+    else
         for (int p = 0; p < npers; ++p) {
             const size_t o = (size_t)p * n * (T + 1) * D;
-            RC(ROWOP(c, mmdm_mdm_pack_planes, S.att + (size_t)p * n * T * D, cond + (size_t)p * D, ldc, m.time_tab, c.h->d_step, m.pe, S.h + o,
-                     reinterpret_cast<uint16_t*>(S.xn) + o, (int64_t)RD, n, T, D, c.st));
+            RC(c.ro.mdm_pack(S.att + (size_t)p * n * T * D, cond + (size_t)p * D, ldc, m.time_tab, c.h->d_step, m.pe, S.h + o, planes ? planes + o : nullptr, (int64_t)RD,
+                             c.rows(n, T), 0, D, c.st));
         }
-        for (int l = 0; l < Lm; ++l)
-            RC(encoder_layer_split(c, S.h, S.xn, m.enc[l], m.st.w_packed, nseq, T + 1, D, m.st.H, m.st.F, 1e-5f, S.qkv, S.att, S.kv, S.f1, l + 1 == Lm));
-        RC(ROWOP(c, mmdm_mdm_unpack, S.h, S.att, nseq, T, D, c.st));
-    } else if (c.rag()) {
-        const Geom& g = *c.g;
-        if (!g.tk.rows) return mmdm_set_error(MMDM_ERR_STATE, "ragged MDM denoiser: the call has no token maps");
-        const int groups = nseq / g.B;
-        const mmdm_rag_seq tseq{g.tok_seq_off, g.tok_seq_len, groups * g.tk.rows, T + 1, g.item_order, g.B};
-        RC(ROWOP(c, mmdm_mdm_pack_rag, S.att, cond, ldc, m.time_tab, c.h->d_step, m.pe, S.h, groups, n / g.B, D, g.rg, g.tk, c.st));
-        for (int l = 0; l < m.st.L; ++l)
-            RC(encoder_layer(c, S.h, m.enc[l], nseq, T + 1, D, m.st.H, m.st.F, false, MMDM_EPI_BIAS_GELU, false, 1e-5f, S.qkv, S.att, S.xn, S.f1, &tseq, g.tok_tt,
-                             (double)g.real_rows + g.B));
-        RC(ROWOP(c, mmdm_mdm_unpack_rag, S.h, S.att, groups, D, g.rg, g.tk, c.st));
-    } else {
-        for (int p = 0; p < npers; ++p)
-            RC(ROWOP(c, mmdm_mdm_pack, S.att + (size_t)p * n * T * D, cond + (size_t)p * D, ldc, m.time_tab, c.h->d_step, m.pe,
-                             S.h + (size_t)p * n * (T + 1) * D, n, T, D, c.st));
-        for (int l = 0; l < m.st.L; ++l)
-            RC(encoder_layer(c, S.h, m.enc[l], nseq, T + 1, D, m.st.H, m.st.F, false, MMDM_EPI_BIAS_GELU, false, 1e-5f, S.qkv, S.att, S.xn, S.f1));
-        RC(ROWOP(c, mmdm_mdm_unpack, S.h, S.att, nseq, T, D, c.st));
+    // the attention writes the rows of the sequences only: the padding token rows of its output planes are zeroed once (S.att held fp32 embeddings)
+    if (split && rag) HIPCHK(hipMemsetAsync(S.att, 0, RD * 2 * sizeof(uint16_t), c.st));
+    for (int l = 0; l < m.st.L; ++l) {
+        if (split) RC(encoder_layer_split(c, S.h, S.xn, m.enc[l], m.st.w_packed, nseq, T + 1, D, m.st.H, m.st.F, 1e-5f, S.qkv, S.att, S.kv, S.f1, l + 1 == m.st.L, tseq));
+        else RC(encoder_layer(c, S.h, m.enc[l], nseq, T + 1, D, m.st.H, m.st.F, false, MMDM_EPI_BIAS_GELU, false, 1e-5f, S.qkv, S.att, S.xn, S.f1, tseq));
     }
+    // extract the frames (drop the conditioning tokens), then the pose head per person
+    RC(c.ro.mdm_unpack(S.h, S.att, c.rows(nseq, T), D, c.st));
     for (int p = 0; p < npers; ++p)
         RC(linear(c, S.att + c.rows_of(p * n, T) * D, D, m.out_w, D, m.out_b, out + (size_t)p * NF, ldo, (int)c.rows_of(n, T), NF, D));
     return MMDM_OK;
@@ -966,11 +974,8 @@ int mixer_core(const Ctx& c, int B, int T) {
     mmdm_handle H = c.h;
     const int n = 2 * B, Dm = H->mx.st.D;
     const mmdm_config& cf = H->cfg;
-    const bool rag = c.rag();
     const size_t nT = c.rows_of(n, T);               // frame rows of the CFG-doubled batch (uniform: n * T)
-    if (rag) RC(mmdm_mixer_pre_rag(H->o1, H->o2, H->d_stats, H->out1, H->out2, n / B, cf.align, c.g->rg, c.st));
-    else if (c.klast) RC(mmdm_mixer_pre_last(H->o1, H->o2, H->d_stats, H->out1, H->out2, n, T, cf.align, c.klast, c.kmask_rows, c.st));
-    else RC(mmdm_mixer_pre_f32(H->o1, H->o2, H->d_stats, H->out1, H->out2, n, T, cf.align, c.st));
+    RC(mmdm_mixer_pre(H->o1, H->o2, H->d_stats, H->out1, H->out2, c.rows(n, T), cf.align, c.klast, c.kmask_rows, c.st));
     // motion_embed + PE of the four streams (mixermdm.py:722-732); seq = p*n + b
     RC(repack(c, H->mx, H->out1, NF2, H->sa.xp, 2, (int)nT));
     RC(repack(c, H->mx, H->out2, NF2, H->sb.xp, 2, (int)nT));
@@ -987,7 +992,7 @@ int mixer_core(const Ctx& c, int B, int T) {
     }
     if (split) {
         // the two Influence calls (mixermdm.py:735-736: person 1, person 2) are independent: one per stream (64.7 -> 64.2 ms/step)
-        Ctx c2{H, H->st2, &H->sb, c.g, c.kmask, c.klast, c.kmask_rows};
+        const Ctx c2 = c.on(H->st2, &H->sb);
         StackRun r1 = r, r2 = r;
         r1.nseq = r2.nseq = n;
         r1.sa_rows = r2.sa_rows = n;
@@ -1006,8 +1011,7 @@ int mixer_core(const Ctx& c, int B, int T) {
     // Influence.out + sigmoid (influence.py:124-125) as a GEMM with a sigmoid epilogue: N = 1 or 23 columns of a 64-wide MFMA tile --
     // wasteful per flop and still 8x faster than a wave-per-row dot-product kernel at 19 200 rows
     if (mode == 1 || mode == 3) {
-        if (rag) RC(ROWOP(c, mmdm_mean_time_rag, c.s->h, H->hpool, 2 * n, c.g->seq_off, c.g->seq_len, Dm, c.st));
-        else RC(ROWOP(c, mmdm_mean_time_f32, c.s->h, H->hpool, 2 * n, T, Dm, c.st));
+        RC(c.ro.mean_time(c.s->h, H->hpool, c.rows(2 * n, T), Dm, c.st));
         RC(linear(c, H->hpool, Dm, H->mx.out_w, Dm, H->mx.out_b, H->w23, H->nw, 2 * n, H->nw, Dm, MMDM_EPI_BIAS_SIGMOID));
     } else {
         RC(linear(c, c.s->h, Dm, H->mx.out_w, Dm, H->mx.out_b, H->w23, H->nw, (int)(2 * nT), H->nw, Dm, MMDM_EPI_BIAS_SIGMOID));
@@ -1015,8 +1019,8 @@ int mixer_core(const Ctx& c, int B, int T) {
     // history destinations come from the device-side descriptor: the launches below are identical whether or not (and where) a call
     // keeps history, so one captured graph serves all of them; the two copy kernels return at once on a null destination
     const int* lp = H->d_step + 1;
-    if (rag) RC(mmdm_blend_cfg_rag(H->out1, H->out2, H->w23, mode, cf.use_force, cf.force_val, cf.cfg_scale, H->model_out, H->d_hist, lp, c.g->rg, c.st));
-    else RC(mmdm_blend_cfg_dyn(H->out1, H->out2, H->w23, mode, cf.use_force, cf.force_val, cf.cfg_scale, H->model_out, H->d_hist, lp, B, T, c.st));
+    RC(mmdm_blend_cfg(H->out1, H->out2, H->w23, mode, cf.use_force, cf.force_val, cf.cfg_scale, H->model_out, nullptr, nullptr, nullptr, H->d_hist, lp,
+                      c.rows(B, T), c.st));
     RC(mmdm_hist_copy(H->out1, H->d_hist, 0, nT * NF2, lp, c.st));
     RC(mmdm_hist_copy(H->out2, H->d_hist, 1, nT * NF2, lp, c.st));
     return MMDM_OK;
@@ -1051,7 +1055,7 @@ int run_step(const Ctx& c) {
     }
     const bool dual = H->cfg.single_only == 3;
     // x_start of the call (mmdm_begin_opts): both chains' root ground paths are overwritten before the models run -- the first node of the step
-    if (H->pinned) RC(c.rag() ? mmdm_pin_root_rag(H->x, H->x2, H->d_opts, c.g->rg, c.st) : mmdm_pin_root(H->x, H->x2, H->d_opts, B, T, c.st));
+    if (H->pinned) RC(mmdm_pin_root(H->x, H->x2, H->d_opts, c.rows(B, T), c.st));
     // the individual model on both persons: in2IN blocks, the "dual_individual" variant of them, or MDMDenoiser
     auto model1 = [&](const Ctx& cc) -> int {
         if (H->d1.kind == 1) return run_denoiser_mdm(cc, H->d1, H->x, B, 2, NF2, n, T, H->cond_cat + 3 * H->cfg.text_dim, H->cond_w, H->o1, NF2);
@@ -1062,7 +1066,7 @@ int run_step(const Ctx& c) {
     if (H->overlap && !H->prof.on) {
         // fork: denoiser2 (with its AdaLN-projection GEMM) on the auxiliary stream with its own scratch; denoiser1 and the mixer's
         // projections on the caller's stream (denoiser1 is the shorter model); join before the mixer
-        Ctx c2{H, H->st2, &H->sb, c.g, c.kmask, c.klast, c.kmask_rows};
+        const Ctx c2 = c.on(H->st2, &H->sb);
         HIPCHK(hipEventRecord(H->ev_fork, c.st));
         HIPCHK(hipStreamWaitEvent(H->st2, H->ev_fork, 0));
         RC(cond_vectors(c2, H->d2, H->txt_d2, H->se_d2, H->ss_d2, 3 * n));
@@ -1085,14 +1089,8 @@ int run_step(const Ctx& c) {
         return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
     }
     RC(mixer_core(c, B, T));
-    if (c.rag() && H->noise_form) RC(mmdm_xstart_ddim_noise_rag(H->noise_form, H->model_out, H->d_stats, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts,
-                                                                H->x, H->x2, H->px1, H->px2, H->floor_ws, H->cfg.xstart_align, c.g->rg, c.st));
-    else if (c.rag()) RC(mmdm_xstart_ddim_rag(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
-                                              H->cfg.xstart_align, c.g->rg, c.st));
-    else if (H->noise_form) RC(mmdm_xstart_ddim_noise(H->noise_form, H->model_out, H->d_stats, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts,
-                                                      H->x, H->x2, H->px1, H->px2, H->floor_ws, B, T, H->cfg.xstart_align, c.st));
-    else RC(mmdm_xstart_ddim_f32(H->model_out, H->d_stats, H->d_coef, H->S, H->d_step, H->x, H->x2, H->px1, H->px2, H->floor_ws,
-                                 B, T, H->cfg.xstart_align, c.st));
+    RC(mmdm_xstart_ddim(H->noise_form, H->model_out, H->d_stats, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts, H->x, H->x2, H->px1, H->px2,
+                        H->floor_ws, c.rows(B, T), H->cfg.xstart_align, c.st));
     return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
 }
 
@@ -1163,6 +1161,13 @@ struct ProfPause {
     explicit ProfPause(Prof& pr) : p(pr), was(pr.on) { p.on = false; }
     ~ProfPause() { p.on = was; }
 };
+
+// the graph key of the handle's begun call (GraphKey says what each field stands for)
+GraphKey graph_key(mmdm_handle h, int masked) {
+    const Geom& g = h->geom;
+    if (!g.rag) return GraphKey{h->B, h->T, h->S, 0, masked, 0, 0, h->noise_form, h->pinned ? 1 : 0};
+    return GraphKey{h->B, (h->T + 63) / 64, h->S, g.rows, masked, g.tk.rows, g.tk.rows ? (h->T + 1 + 63) / 64 : 0, h->noise_form, h->pinned ? 1 : 0};
+}
 
 int push_hist(mmdm_handle h, hipStream_t st) { return mmdm_set_hist_desc(h->d_hist, h->hist, st); }
 
@@ -1836,13 +1841,9 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
         hipGraphExec_t exec = nullptr;
         hipEvent_t done = nullptr;
         int first = 0;
-        // what a captured node bakes in: uniform (B, T, S); ragged (B, query tiles of the longest item, S, group stride) -- the lengths are device data
-        // (+ with MDM as denoiser 1: the token stride and the query tiles of the longest token sequence, T + 1 rows)
-        const int kT = h->geom.rag ? (h->T + 63) / 64 : h->T, kR = h->geom.rag ? h->geom.rows : 0;
-        const int kTR = h->geom.rag ? h->geom.tk.rows : 0, kTT = kTR ? (h->T + 1 + 63) / 64 : 0;
+        const GraphKey key = graph_key(h, masked);
         for (auto& g : h->graphs)
-            if (g.B == h->B && g.T == kT && g.S == h->S && g.rows == kR && g.masked == masked && g.trows == kTR && g.tT == kTT && g.noise == h->noise_form &&
-                g.pinned == (h->pinned ? 1 : 0)) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
+            if (g.key == key) { exec = g.exec; done = g.done; g.used = ++h->graph_clock; break; }
         if (!exec) {
             hipGraph_t g = nullptr;
             // one capture at a time in the process: several handles may be driven from several host threads (mmdm_create_shared), and two
@@ -1876,7 +1877,7 @@ extern "C" int mmdm_run(mmdm_handle h, int nsteps, int use_graph, void* stream) 
                 (void)hipGraphExecDestroy(exec);
                 return herr(h, mmdm_set_error(MMDM_ERR_HIP, "mmdm_run: hipEventCreate: %s", hipGetErrorString(e)));
             }
-            h->graphs.push_back({h->B, kT, h->S, kR, exec, ++h->graph_clock, done, masked, kTR, kTT, h->noise_form, h->pinned ? 1 : 0});
+            h->graphs.push_back({key, exec, ++h->graph_clock, done});
             ++h->n_captures;
             // the FIRST launch of a fresh exec binds the runtime's internal branch streams to it (hip::Graph::UpdateStreams): still inside the
             // exclusive section -- beside another thread's launch that is where the runtime was seen to crash

@@ -5,10 +5,11 @@
 #include "kernels.h"
 
 // This file is built TWICE (mixermdm_amd/build.py): rowops.o as it stands, and rowops_nopk.o with -DMMDM_ROWOPS_NOPK and without the packed-fp32
-// VALU instructions -- the same kernels (inside `nopk::`, so that a kernel trace tells them apart) behind entry points named *_nopk, which the
-// handles of precision 1-3 take (mmdm.hip ROWOP): their row kernels run beside packed-W GEMMs, where dense packed-fp32 code was seen to
-// compute other bits on gfx950 (build.py has the story; AdaLN itself was never seen to move -- tests/test_gpu_hazard.py holds that -- the
-// second build removes the question instead of answering it).  The stateless entry points of include/mmdm.h exist in the first build only.
+// VALU instructions -- the same kernels (inside `nopk::`, so that a kernel trace tells them apart).  Each build fills its own table of row operations
+// (kernels.h mmdm_rowops: mmdm_rowops_tab / mmdm_rowops_tab_nopk); the handles of precision 1-3 take the second (mmdm.hip Ctx::ro): their row kernels run
+// beside packed-W GEMMs, where dense packed-fp32 code was seen to compute other bits on gfx950 (build.py has the story; AdaLN itself was never seen to
+// move -- tests/test_gpu_hazard.py holds that -- the second build removes the question instead of answering it).  The entry points of include/mmdm.h
+// exist in the first build only.
 #ifdef MMDM_ROWOPS_NOPK
 #define RO(name) name##_nopk
 #else
@@ -460,35 +461,13 @@ __global__ void gauss1d_kernel(const float* __restrict__ x, float* __restrict__ 
 #endif
 }  // namespace
 
-#ifndef MMDM_ROWOPS_NOPK
-extern "C" int mmdm_gaussian_filter1d_f32(const float* x, float* out, const double* weights, int radius, int n, int T, int C, void* stream) {
-    if (n == 0 || T == 0 || C == 0) return MMDM_OK;
-    if (!x || !out || !weights || radius < 0 || n < 0 || T < 0 || C < 0 || x == out)
-        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_gaussian_filter1d_f32: bad arguments (in-place is not supported)");
-    const size_t total = (size_t)n * T * C;
-    hipLaunchKernelGGL(gauss1d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, weights, radius, n, T, C);
-    return mmdm_check_launch("gauss1d");
-}
-
-extern "C" int mmdm_adaln_f32(const float* h, const float* ss, int ss_ld, int ss_rows, float* out, int nseq, int T, int D, void* stream) {
-    return mmdm_adaln_ex(h, ss, ss_ld, ss_rows, out, 0, nseq, T, D, stream);
-}
-
-extern "C" int mmdm_adaln_ex(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_bf16, int nseq, int T, int D, void* stream) {
-    if (out_bf16 < 0 || out_bf16 > 2) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_adaln_ex: output mode must be 0 (fp32), 1 (bf16) or 2 (the two fp16 planes of the fp32-split mode)");
-    return mmdm_adaln_any(h, ss, ss_ld, ss_rows, out, out_bf16, nullptr, nseq, T, D, stream);
-}
-
-extern "C" int mmdm_adaln_fp8(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, float* row_scale, int nseq, int T, int D, void* stream) {
-    if (!row_scale) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_adaln_fp8: null row_scale");
-    return mmdm_adaln_any(h, ss, ss_ld, ss_rows, out, 3, row_scale, nseq, T, D, stream);
-}
-
-#endif  // !MMDM_ROWOPS_NOPK
-
+// ------------------------------------------------------------------------------------------------------
+// Host side.  The launchers of this build's row operations have internal linkage: the rest of the library reaches them through the build's table
+// (kernels.h mmdm_rowops; defined below them), the stateless entry points of include/mmdm.h -- first build only -- forward to them.
+// ------------------------------------------------------------------------------------------------------
 // row_seq != nullptr: ragged batch -- `rows_rag` rows in all, row r belongs to sequence row_seq[r] (device array); nseq / T are then unused
-int RO(mmdm_adaln_any)(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_bf16, float* row_scale, int nseq, int T, int D, void* stream,
-                   const int* row_seq, int rows_rag) {
+static int adaln_any(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_bf16, float* row_scale, int nseq, int T, int D, void* stream,
+                     const int* row_seq, int rows_rag) {
     if (row_seq) { nseq = 1; T = rows_rag; }
     if (nseq == 0 || T == 0) return MMDM_OK;
     if (!h || !ss || !out || nseq < 0 || T < 0 || D <= 0 || ss_rows <= 0 || ss_ld < 2 * D)
@@ -514,7 +493,7 @@ int RO(mmdm_adaln_any)(const float* h, const float* ss, int ss_ld, int ss_rows, 
     return mmdm_check_launch("adaln");
 }
 
-extern "C" int RO(mmdm_layernorm_f32)(const float* x, const float* gamma, const float* beta, float* out, int rows, int D, float eps, void* stream) {
+static int layernorm(const float* x, const float* gamma, const float* beta, float* out, int rows, int D, float eps, void* stream) {
     if (rows == 0) return MMDM_OK;
     if (!x || !gamma || !beta || !out || rows < 0 || D <= 0 || !(eps > 0.f)) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_f32: bad arguments rows=%d D=%d", rows, D);
     if ((D & 3) || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(out)) & 15))
@@ -529,9 +508,9 @@ extern "C" int RO(mmdm_layernorm_f32)(const float* x, const float* gamma, const 
     return mmdm_check_launch("layernorm");
 }
 
-// LayerNorm into the fp32 row AND its two fp16 planes (layernorm_split_kernel); the argument rules of mmdm_layernorm_f32, plus 16-byte aligned planes
-int RO(mmdm_layernorm_planes)(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
-                              hipStream_t st) {
+// LayerNorm into the fp32 row AND its two fp16 planes (layernorm_split_kernel); the argument rules of layernorm, plus 16-byte aligned planes
+static int layernorm_planes(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
+                            hipStream_t st) {
     if (rows == 0) return MMDM_OK;
     if (!x || !gamma || !beta || !out || !planes || rows < 0 || D <= 0 || !(eps > 0.f))
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_split: bad arguments rows=%d D=%d", rows, D);
@@ -541,7 +520,7 @@ int RO(mmdm_layernorm_planes)(const float* x, const float* gamma, const float* b
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_split: the planes must be 16-byte aligned, with a plane stride >= rows * D that is a multiple of 8 (stride=%lld)",
                               (long long)plane_stride);
     if (D > 64 * 4 * 8) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_layernorm_split: D=%d > 2048", D);
-    dim3 grid(min((rows + 3) / 4, 2048)), block(256);          // persistent wave slots, as mmdm_layernorm_f32
+    dim3 grid(min((rows + 3) / 4, 2048)), block(256);          // persistent wave slots, as layernorm
     _Float16* pl = static_cast<_Float16*>(planes);
     const size_t ps = (size_t)plane_stride;
     if (D <= 256) hipLaunchKernelGGL((layernorm_split_kernel<1>), grid, block, 0, st, x, gamma, beta, out, pl, ps, rows, D, eps);
@@ -551,74 +530,106 @@ int RO(mmdm_layernorm_planes)(const float* x, const float* gamma, const float* b
     return mmdm_check_launch("layernorm_split");
 }
 
-#ifndef MMDM_ROWOPS_NOPK
-// build: 0 = this object's kernels (the bits of mmdm_layernorm_f32), 1 = the second build's (no packed-fp32 instructions, DPP reductions: what a
-// precision-2 handle runs).  planes == NULL: the plain LayerNorm of that build.
-extern "C" int mmdm_layernorm_split(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
-                                    int build, void* stream) {
-    if (build != 0 && build != 1) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_layernorm_split: build must be 0 or 1");
-    if (!planes) return build ? mmdm_layernorm_f32_nopk(x, gamma, beta, out, rows, D, eps, stream) : mmdm_layernorm_f32(x, gamma, beta, out, rows, D, eps, stream);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return build ? mmdm_layernorm_planes_nopk(x, gamma, beta, out, planes, plane_stride, rows, D, eps, st) : mmdm_layernorm_planes(x, gamma, beta, out, planes, plane_stride, rows, D, eps, st);
+// The sequence assembly: uniform r.n sequences of r.T frames -> T + 1 token rows each; ragged r.n / fr->B frame groups `fr` -> token groups `tk`, `gpp` groups per
+// person (the CFG halves).  planes != null (precision 2): the rows' two fp16 planes as a second output (mdm_pack_split_kernel / mdm_pack_rag_split_kernel)
+static int mdm_pack(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
+                    int64_t plane_stride, const mmdm_rows& r, int gpp, int D, hipStream_t st) {
+    if (r.fr && !r.tk) return mmdm_set_error(MMDM_ERR_STATE, "mdm_pack_rag: no token rows");
+    const int groups = r.fr ? r.n / r.fr->B : 0;
+    const size_t n = (r.fr ? (size_t)groups * r.tk->rows : (size_t)r.n * (r.T + 1)) * (planes ? D >> 2 : D);      // threads: one per element, or per four with planes
+    if (n == 0) return MMDM_OK;
+    if (planes && ((D & 3) || (ldc & 3) || (plane_stride & 7) || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(cond) | reinterpret_cast<uintptr_t>(time_tab) |
+                                                                  reinterpret_cast<uintptr_t>(pe) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(planes)) & 15)))
+        return mmdm_set_error(MMDM_ERR_ARG, "mdm_pack%s (split): D and the cond stride must be multiples of 4 and every row 16-byte aligned (D=%d ldc=%d)", r.fr ? "_rag" : "", D, ldc);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    _Float16* pl = static_cast<_Float16*>(planes);
+    if (r.fr && planes)
+        hipLaunchKernelGGL(mdm_pack_rag_split_kernel, grid, block, 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, pl, (size_t)plane_stride, groups, gpp, D, *r.fr, *r.tk);
+    else if (r.fr) hipLaunchKernelGGL(mdm_pack_rag_kernel, grid, block, 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, *r.fr, *r.tk);
+    else if (planes) hipLaunchKernelGGL(mdm_pack_split_kernel, grid, block, 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, pl, (size_t)plane_stride, r.n, r.T, D);
+    else hipLaunchKernelGGL(mdm_pack_kernel, grid, block, 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, r.n, r.T, D);
+    return mmdm_check_launch(r.fr ? "mdm_pack_rag" : "mdm_pack");
 }
+
+static int mdm_unpack(const float* src, float* dst, const mmdm_rows& r, int D, hipStream_t st) {
+    if (r.fr && !r.tk) return mmdm_set_error(MMDM_ERR_STATE, "mdm_unpack_rag: no token rows");
+    const int groups = r.fr ? r.n / r.fr->B : 0;
+    const size_t n = (r.fr ? (size_t)groups * r.fr->rows : (size_t)r.n * r.T) * D;
+    if (n == 0) return MMDM_OK;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (r.fr) hipLaunchKernelGGL(mdm_unpack_rag_kernel, grid, block, 0, st, src, dst, groups, D, *r.fr, *r.tk);
+    else hipLaunchKernelGGL(mdm_unpack_kernel, grid, block, 0, st, src, dst, r.n, r.T, D);
+    return mmdm_check_launch(r.fr ? "mdm_unpack_rag" : "mdm_unpack");
+}
+
+static int cond_silu(const float* time_tab, const int* step_idx, const float* txt, float* out, int rows, int D, void* stream) {
+    if (rows == 0) return MMDM_OK;
+    if (!time_tab || !step_idx || !txt || !out || rows < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_cond_silu_f32: bad arguments");
+    const size_t n = (size_t)rows * D;
+    hipLaunchKernelGGL(cond_silu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), time_tab, step_idx, txt, out, rows, D);
+    return mmdm_check_launch("cond_silu");
+}
+
+static int cond_silu_planes(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st) {
+    if (rows == 0) return MMDM_OK;
+    const size_t n = (size_t)rows * D;
+    hipLaunchKernelGGL(cond_silu_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, time_tab, step_idx, txt, out, plane, rows, D);
+    return mmdm_check_launch("cond_silu_planes");
+}
+
+// ragged (r.seq_off): sequence s = rows [seq_off[s], seq_off[s] + seq_len[s]) of h
+static int mean_time(const float* h, float* out, const mmdm_rows& r, int D, hipStream_t st) {
+    if (r.n == 0) return MMDM_OK;
+    if (r.seq_off) {
+        hipLaunchKernelGGL(mean_time_rag_kernel, dim3((D + 255) / 256, r.n), dim3(256), 0, st, h, out, r.seq_off, r.seq_len, D);
+        return mmdm_check_launch("mean_time_rag");
+    }
+    if (!h || !out || r.n < 0 || r.T <= 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_mean_time_f32: bad arguments");
+    hipLaunchKernelGGL(mean_time_kernel, dim3((D + 255) / 256, r.n), dim3(256), 0, st, h, out, r.T, D);
+    return mmdm_check_launch("mean_time");
+}
+
+// (host pass only: the device pass would emit a constant of external linkage too, and has no such functions to point at)
+#ifndef __HIP_DEVICE_COMPILE__
+const mmdm_rowops RO(mmdm_rowops_tab) = {adaln_any, layernorm, layernorm_planes, cond_silu, cond_silu_planes, mean_time, mdm_pack, mdm_unpack};
 #endif
 
-int RO(mmdm_mdm_pack)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
-                  int nseq, int T, int D, hipStream_t st) {
-    const size_t n = (size_t)nseq * (T + 1) * D;
-    if (n == 0) return MMDM_OK;
-    hipLaunchKernelGGL(mdm_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, nseq, T, D);
-    return mmdm_check_launch("mdm_pack");
-}
-
-int RO(mmdm_mdm_unpack)(const float* src, float* dst, int nseq, int T, int D, hipStream_t st) {
-    const size_t n = (size_t)nseq * T * D;
-    if (n == 0) return MMDM_OK;
-    hipLaunchKernelGGL(mdm_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, nseq, T, D);
-    return mmdm_check_launch("mdm_unpack");
-}
-
-int RO(mmdm_mdm_pack_rag)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst,
-                          int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st) {
-    const size_t n = (size_t)groups * tk.rows * D;
-    if (n == 0) return MMDM_OK;
-    hipLaunchKernelGGL(mdm_pack_rag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, fr, tk);
-    return mmdm_check_launch("mdm_pack_rag");
-}
-
-// the two assembly passes with the rows' fp16 planes as a second output (precision 2: mdm_pack_split_kernel / mdm_pack_rag_split_kernel)
-int RO(mmdm_mdm_pack_planes)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
-                             int64_t plane_stride, int nseq, int T, int D, hipStream_t st) {
-    const size_t n = (size_t)nseq * (T + 1) * (D >> 2);
-    if (n == 0) return MMDM_OK;
-    if ((D & 3) || (ldc & 3) || (plane_stride & 7) || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(cond) | reinterpret_cast<uintptr_t>(time_tab) |
-                                                      reinterpret_cast<uintptr_t>(pe) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(planes)) & 15))
-        return mmdm_set_error(MMDM_ERR_ARG, "mdm_pack (split): D and the cond stride must be multiples of 4 and every row 16-byte aligned (D=%d ldc=%d)", D, ldc);
-    hipLaunchKernelGGL(mdm_pack_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst,
-                       static_cast<_Float16*>(planes), (size_t)plane_stride, nseq, T, D);
-    return mmdm_check_launch("mdm_pack_split");
-}
-
-int RO(mmdm_mdm_pack_rag_planes)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
-                                 int64_t plane_stride, int groups, int gpp, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st) {
-    const size_t n = (size_t)groups * tk.rows * (D >> 2);
-    if (n == 0) return MMDM_OK;
-    if ((D & 3) || (ldc & 3) || (plane_stride & 7) || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(cond) | reinterpret_cast<uintptr_t>(time_tab) |
-                                                      reinterpret_cast<uintptr_t>(pe) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(planes)) & 15))
-        return mmdm_set_error(MMDM_ERR_ARG, "mdm_pack_rag (split): D and the cond stride must be multiples of 4 and every row 16-byte aligned (D=%d ldc=%d)", D, ldc);
-    hipLaunchKernelGGL(mdm_pack_rag_split_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, cond, ldc, time_tab, step_idx, pe, dst,
-                       static_cast<_Float16*>(planes), (size_t)plane_stride, groups, gpp, D, fr, tk);
-    return mmdm_check_launch("mdm_pack_rag_split");
-}
-
-int RO(mmdm_mdm_unpack_rag)(const float* src, float* dst, int groups, int D, const mmdm_rag& fr, const mmdm_rag& tk, hipStream_t st) {
-    const size_t n = (size_t)groups * fr.rows * D;
-    if (n == 0) return MMDM_OK;
-    hipLaunchKernelGGL(mdm_unpack_rag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, groups, D, fr, tk);
-    return mmdm_check_launch("mdm_unpack_rag");
-}
-
 #ifndef MMDM_ROWOPS_NOPK
+extern "C" int mmdm_gaussian_filter1d_f32(const float* x, float* out, const double* weights, int radius, int n, int T, int C, void* stream) {
+    if (n == 0 || T == 0 || C == 0) return MMDM_OK;
+    if (!x || !out || !weights || radius < 0 || n < 0 || T < 0 || C < 0 || x == out)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_gaussian_filter1d_f32: bad arguments (in-place is not supported)");
+    const size_t total = (size_t)n * T * C;
+    hipLaunchKernelGGL(gauss1d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, weights, radius, n, T, C);
+    return mmdm_check_launch("gauss1d");
+}
+
+extern "C" int mmdm_adaln_f32(const float* h, const float* ss, int ss_ld, int ss_rows, float* out, int nseq, int T, int D, void* stream) {
+    return mmdm_adaln_ex(h, ss, ss_ld, ss_rows, out, 0, nseq, T, D, stream);
+}
+
+extern "C" int mmdm_adaln_ex(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_bf16, int nseq, int T, int D, void* stream) {
+    if (out_bf16 < 0 || out_bf16 > 2) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_adaln_ex: output mode must be 0 (fp32), 1 (bf16) or 2 (the two fp16 planes of the fp32-split mode)");
+    return adaln_any(h, ss, ss_ld, ss_rows, out, out_bf16, nullptr, nseq, T, D, stream, nullptr, 0);
+}
+
+extern "C" int mmdm_adaln_fp8(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, float* row_scale, int nseq, int T, int D, void* stream) {
+    if (!row_scale) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_adaln_fp8: null row_scale");
+    return adaln_any(h, ss, ss_ld, ss_rows, out, 3, row_scale, nseq, T, D, stream, nullptr, 0);
+}
+
+extern "C" int mmdm_layernorm_f32(const float* x, const float* gamma, const float* beta, float* out, int rows, int D, float eps, void* stream) {
+    return layernorm(x, gamma, beta, out, rows, D, eps, stream);
+}
+
+extern "C" int mmdm_cond_silu_f32(const float* time_tab, const int* step_idx, const float* txt, float* out, int rows, int D, void* stream) {
+    return cond_silu(time_tab, step_idx, txt, out, rows, D, stream);
+}
+
+extern "C" int mmdm_mean_time_f32(const float* h, float* out, int nseq, int T, int D, void* stream) {
+    return mean_time(h, out, mmdm_rows{nseq, T}, D, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int mmdm_token_embed_f32(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, void* stream) {
     if (n == 0 || L == 0) return MMDM_OK;
     if (!table || !tokens || !pos || !out || n < 0 || L < 0 || D <= 0 || vocab <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_token_embed_f32: bad arguments");
@@ -627,37 +638,6 @@ extern "C" int mmdm_token_embed_f32(const float* table, int vocab, const int* to
     return mmdm_check_launch("token_embed");
 }
 
-#endif
-
-extern "C" int RO(mmdm_cond_silu_f32)(const float* time_tab, const int* step_idx, const float* txt, float* out, int rows, int D, void* stream) {
-    if (rows == 0) return MMDM_OK;
-    if (!time_tab || !step_idx || !txt || !out || rows < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_cond_silu_f32: bad arguments");
-    const size_t n = (size_t)rows * D;
-    hipLaunchKernelGGL(cond_silu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), time_tab, step_idx, txt, out, rows, D);
-    return mmdm_check_launch("cond_silu");
-}
-
-int RO(mmdm_cond_silu_planes)(const float* time_tab, const int* step_idx, const float* txt, _Float16* out, size_t plane, int rows, int D, hipStream_t st) {
-    if (rows == 0) return MMDM_OK;
-    const size_t n = (size_t)rows * D;
-    hipLaunchKernelGGL(cond_silu_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, time_tab, step_idx, txt, out, plane, rows, D);
-    return mmdm_check_launch("cond_silu_planes");
-}
-
-extern "C" int RO(mmdm_mean_time_f32)(const float* h, float* out, int nseq, int T, int D, void* stream) {
-    if (nseq == 0) return MMDM_OK;
-    if (!h || !out || nseq < 0 || T <= 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_mean_time_f32: bad arguments");
-    hipLaunchKernelGGL(mean_time_kernel, dim3((D + 255) / 256, nseq), dim3(256), 0, static_cast<hipStream_t>(stream), h, out, T, D);
-    return mmdm_check_launch("mean_time");
-}
-
-int RO(mmdm_mean_time_rag)(const float* h, float* out, int nseq, const int* seq_off, const int* seq_len, int D, hipStream_t st) {
-    if (nseq == 0) return MMDM_OK;
-    hipLaunchKernelGGL(mean_time_rag_kernel, dim3((D + 255) / 256, nseq), dim3(256), 0, st, h, out, seq_off, seq_len, D);
-    return mmdm_check_launch("mean_time_rag");
-}
-
-#ifndef MMDM_ROWOPS_NOPK
 extern "C" int mmdm_influence_head_f32(const float* h, const float* Wout, const float* bout, float* w, int rows, int D, int nw, void* stream) {
     if (rows == 0) return MMDM_OK;
     if (!h || !Wout || !bout || !w || rows < 0 || D <= 0 || nw <= 0 || nw > 23)
@@ -666,61 +646,70 @@ extern "C" int mmdm_influence_head_f32(const float* h, const float* Wout, const 
     return mmdm_check_launch("influence_head");
 }
 
-// Diagnostic entry points (include/mmdm.h, beside mmdm_layernorm_split): every row operation in either build, for tests/test_gpu_rowops.py.  Argument
-// checks and dispatch only -- the kernels and their launch code are the ones the handles run (ROWOP in mmdm.hip).
-#define ROWOP_BUILD(what)                                                                                         \
-    if (build != 0 && build != 1) return mmdm_set_error(MMDM_ERR_ARG, what ": build must be 0 or 1")
+// Diagnostic entry points (include/mmdm.h): every row operation in either build, for tests/test_gpu_rowops.py.  Argument checks only -- the launch code is the
+// table's, i.e. what the handles run.  build: 0 = this object's kernels (the bits of mmdm_layernorm_f32), 1 = the second build's (no packed-fp32
+// instructions, DPP reductions: what a precision 1-3 handle runs).
+static const mmdm_rowops* rowops_of(int build, const char* who) {
+    if (build != 0 && build != 1) { mmdm_set_error(MMDM_ERR_ARG, "%s: build must be 0 or 1", who); return nullptr; }
+    return build ? &mmdm_rowops_tab_nopk : &mmdm_rowops_tab;
+}
+
+// planes == NULL: the plain LayerNorm of that build
+extern "C" int mmdm_layernorm_split(const float* x, const float* gamma, const float* beta, float* out, void* planes, int64_t plane_stride, int rows, int D, float eps,
+                                    int build, void* stream) {
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_layernorm_split");
+    if (!ro) return MMDM_ERR_ARG;
+    if (!planes) return ro->layernorm(x, gamma, beta, out, rows, D, eps, stream);
+    return ro->layernorm_planes(x, gamma, beta, out, planes, plane_stride, rows, D, eps, static_cast<hipStream_t>(stream));
+}
 
 extern "C" int mmdm_rowop_adaln(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_mode, float* row_scale, int nseq, int T, int D,
                                 const int* row_seq, int rows_rag, int build, void* stream) {
-    ROWOP_BUILD("mmdm_rowop_adaln");
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_adaln");
+    if (!ro) return MMDM_ERR_ARG;
     if (out_mode < 0 || out_mode > 3) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_adaln: output mode must be 0 (fp32), 1 (bf16), 2 (two fp16 planes) or 3 (fp8 + row_scale)");
     if (out_mode == 3 && !row_scale) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_adaln: null row_scale");
     if (row_seq && rows_rag < 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_adaln: rows_rag=%d", rows_rag);
-    return build ? mmdm_adaln_any_nopk(h, ss, ss_ld, ss_rows, out, out_mode, row_scale, nseq, T, D, stream, row_seq, rows_rag)
-                 : mmdm_adaln_any(h, ss, ss_ld, ss_rows, out, out_mode, row_scale, nseq, T, D, stream, row_seq, rows_rag);
+    return ro->adaln(h, ss, ss_ld, ss_rows, out, out_mode, row_scale, nseq, T, D, stream, row_seq, rows_rag);
 }
 
 extern "C" int mmdm_rowop_cond_silu(const float* time_tab, const int* step_idx, const float* txt, void* out, int planes, int64_t plane_stride, int rows, int D,
                                     int build, void* stream) {
-    ROWOP_BUILD("mmdm_rowop_cond_silu");
-    if (!planes) return build ? mmdm_cond_silu_f32_nopk(time_tab, step_idx, txt, static_cast<float*>(out), rows, D, stream)
-                              : mmdm_cond_silu_f32(time_tab, step_idx, txt, static_cast<float*>(out), rows, D, stream);
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_cond_silu");
+    if (!ro) return MMDM_ERR_ARG;
+    if (!planes) return ro->cond_silu(time_tab, step_idx, txt, static_cast<float*>(out), rows, D, stream);
     if (rows == 0) return MMDM_OK;
     if (!time_tab || !step_idx || !txt || !out || rows < 0 || D <= 0 || plane_stride < (int64_t)rows * D)
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_cond_silu: bad arguments rows=%d D=%d plane stride=%lld", rows, D, (long long)plane_stride);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return build ? mmdm_cond_silu_planes_nopk(time_tab, step_idx, txt, static_cast<_Float16*>(out), (size_t)plane_stride, rows, D, st)
-                 : mmdm_cond_silu_planes(time_tab, step_idx, txt, static_cast<_Float16*>(out), (size_t)plane_stride, rows, D, st);
+    return ro->cond_silu_planes(time_tab, step_idx, txt, static_cast<_Float16*>(out), (size_t)plane_stride, rows, D, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmdm_rowop_mean_time(const float* h, float* out, int nseq, int T, const int* seq_off, const int* seq_len, int D, int build, void* stream) {
-    ROWOP_BUILD("mmdm_rowop_mean_time");
-    if (!seq_off && !seq_len) return build ? mmdm_mean_time_f32_nopk(h, out, nseq, T, D, stream) : mmdm_mean_time_f32(h, out, nseq, T, D, stream);
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_mean_time");
+    if (!ro) return MMDM_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!seq_off && !seq_len) return ro->mean_time(h, out, mmdm_rows{nseq, T}, D, st);
     if (nseq == 0) return MMDM_OK;
     if (!h || !out || !seq_off || !seq_len || nseq < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mean_time: bad arguments (ragged: seq_off AND seq_len)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return build ? mmdm_mean_time_rag_nopk(h, out, nseq, seq_off, seq_len, D, st) : mmdm_mean_time_rag(h, out, nseq, seq_off, seq_len, D, st);
+    return ro->mean_time(h, out, mmdm_rows{nseq, 0, nullptr, nullptr, seq_off, seq_len}, D, st);
 }
 
 extern "C" int mmdm_rowop_mdm_pack(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
                                    int64_t plane_stride, int nseq, int T, int D, int build, void* stream) {
-    ROWOP_BUILD("mmdm_rowop_mdm_pack");
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_mdm_pack");
+    if (!ro) return MMDM_ERR_ARG;
     if (nseq == 0) return MMDM_OK;
     if (!src || !cond || !time_tab || !step_idx || !pe || !dst || nseq < 0 || T < 0 || D <= 0 || ldc < D || (planes && plane_stride < (int64_t)nseq * (T + 1) * D))
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_pack: bad arguments nseq=%d T=%d D=%d ldc=%d", nseq, T, D, ldc);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (planes) return build ? mmdm_mdm_pack_planes_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, nseq, T, D, st)
-                             : mmdm_mdm_pack_planes(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, nseq, T, D, st);
-    return build ? mmdm_mdm_pack_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, nseq, T, D, st) : mmdm_mdm_pack(src, cond, ldc, time_tab, step_idx, pe, dst, nseq, T, D, st);
+    return ro->mdm_pack(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, mmdm_rows{nseq, T}, 0, D, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmdm_rowop_mdm_unpack(const float* src, float* dst, int nseq, int T, int D, int build, void* stream) {
-    ROWOP_BUILD("mmdm_rowop_mdm_unpack");
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_mdm_unpack");
+    if (!ro) return MMDM_ERR_ARG;
     if (nseq == 0 || T == 0) return MMDM_OK;
     if (!src || !dst || nseq < 0 || T < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_unpack: bad arguments nseq=%d T=%d D=%d", nseq, T, D);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return build ? mmdm_mdm_unpack_nopk(src, dst, nseq, T, D, st) : mmdm_mdm_unpack(src, dst, nseq, T, D, st);
+    return ro->mdm_unpack(src, dst, mmdm_rows{nseq, T}, D, static_cast<hipStream_t>(stream));
 }
 
 // the two row spaces of a ragged batch as the caller's device arrays (kernels.h mmdm_rag): frame rows fr_*, token rows tk_*
@@ -734,29 +723,25 @@ extern "C" int mmdm_rowop_mdm_pack_rag(const float* src, const float* cond, int 
                                        int64_t plane_stride, int groups, int gpp, int D, int B, int fr_rows, const int* fr_row_item, const int* fr_row_pos,
                                        const int* fr_item_off, const int* fr_item_len, int tk_rows, const int* tk_row_item, const int* tk_row_pos,
                                        const int* tk_item_off, const int* tk_item_len, int build, void* stream) {
-    ROWOP_BUILD("mmdm_rowop_mdm_pack_rag");
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_mdm_pack_rag");
+    if (!ro) return MMDM_ERR_ARG;
     if (groups == 0) return MMDM_OK;
     ROWOP_RAG_CHECK("mmdm_rowop_mdm_pack_rag");
     if (!src || !cond || !time_tab || !step_idx || !pe || !dst || groups < 0 || gpp <= 0 || D <= 0 || ldc < (groups + gpp - 1) / gpp * D ||
         (planes && plane_stride < (int64_t)groups * tk_rows * D))
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_pack_rag: bad arguments groups=%d gpp=%d D=%d ldc=%d", groups, gpp, D, ldc);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (planes) return build ? mmdm_mdm_pack_rag_planes_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, groups, gpp, D, fr, tk, st)
-                             : mmdm_mdm_pack_rag_planes(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, groups, gpp, D, fr, tk, st);
-    return build ? mmdm_mdm_pack_rag_nopk(src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, fr, tk, st)
-                 : mmdm_mdm_pack_rag(src, cond, ldc, time_tab, step_idx, pe, dst, groups, gpp, D, fr, tk, st);
+    return ro->mdm_pack(src, cond, ldc, time_tab, step_idx, pe, dst, planes, plane_stride, mmdm_rows{groups * B, 0, &fr, &tk}, gpp, D, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmdm_rowop_mdm_unpack_rag(const float* src, float* dst, int groups, int D, int B, int fr_rows, const int* fr_row_item, const int* fr_row_pos,
                                          const int* fr_item_off, const int* fr_item_len, int tk_rows, const int* tk_row_item, const int* tk_row_pos,
                                          const int* tk_item_off, const int* tk_item_len, int build, void* stream) {
-    ROWOP_BUILD("mmdm_rowop_mdm_unpack_rag");
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_mdm_unpack_rag");
+    if (!ro) return MMDM_ERR_ARG;
     if (groups == 0) return MMDM_OK;
     ROWOP_RAG_CHECK("mmdm_rowop_mdm_unpack_rag");
     if (!src || !dst || groups < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_mdm_unpack_rag: bad arguments groups=%d D=%d", groups, D);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return build ? mmdm_mdm_unpack_rag_nopk(src, dst, groups, D, fr, tk, st) : mmdm_mdm_unpack_rag(src, dst, groups, D, fr, tk, st);
+    return ro->mdm_unpack(src, dst, mmdm_rows{groups * B, 0, &fr, &tk}, D, static_cast<hipStream_t>(stream));
 }
 #undef ROWOP_RAG_CHECK
-#undef ROWOP_BUILD
 #endif

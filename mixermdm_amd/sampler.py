@@ -537,7 +537,9 @@ class Sampler:
         return out
 
     def graph_stats(self):
-        """(steps captured, steps replayed, graphs cached) of the handle's (B, T, S)-keyed hipGraph cache."""
+        """(steps captured, steps replayed, graphs cached) of the handle's hipGraph cache.  Its key is everything a captured step bakes in: B, T and
+        the schedule's S; whether a key mask is set, the call's noise form and whether it pins x_start; for a ragged call the group stride in rows and
+        the query tiles of the longest item instead of T -- with MDM as denoiser 1 the token stride and token tiles as well (csrc/mmdm.hip GraphKey)."""
         cap, rep, n = C.c_int64(), C.c_int64(), C.c_int()
         check(self.lib.mmdm_graph_stats(self.h, C.byref(cap), C.byref(rep), C.byref(n)), self.h)
         return cap.value, rep.value, n.value

@@ -22,8 +22,9 @@ s = s.replace('constexpr int NF = MMDM_NF, NF2 = 2 * MMDM_NF;', 'constexpr int N
 for name, bit in (("linear", 1), ("attention_plain", 2), ("linear_b", 4), ("linear_8", 8), ("linear_s", 16), ("attention_p", 32), ("attention_b", 64)):
     i = s.index("\nint %s(const Ctx& c" % name); b = s.index("{\n", i)
     s = s[:b + 2] + "    if (g_dbg_skip & %d) return MMDM_OK;\n" % bit + s[b + 2:]
-i = s.index("\nint run_stack(const Ctx& c")
-s = s[:i] + "\n#define mmdm_adaln_any(...) ((g_dbg_skip & 128) ? 0 : mmdm_adaln_any(__VA_ARGS__))" + s[i:]
+marker = "        return c.ro.adaln("            # the AdaLN of run_stack's `norm`
+assert s.count(marker) == 1
+s = s.replace(marker, "        if (g_dbg_skip & 128) return MMDM_OK;\n" + marker, 1)
 s += r'''
 static std::map<void*, std::vector<unsigned char>> g_dbg_snap;
 int mmdm_debug_handle(const char* key, long long value) {
