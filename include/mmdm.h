@@ -377,6 +377,35 @@ size_t mmdm_encoder_layer_workspace(int nseq, int T, int D, int F);
 int mmdm_encoder_layer_f32(float* x, const mmdm_encoder_layer_weights* w, int nseq, int T, int D, int H, int F, int norm_first,
                            int activation, int causal, float eps, float* workspace, size_t workspace_floats, void* stream);
 
+/* The same post-norm layer on a RAGGED batch, in place on packed rows x [total_rows, D]: sequence s owns rows [seq_off[s], seq_off[s] + seq_len[s])
+ * (DEVICE int arrays [nseq], every length >= 1; max_len >= every length sizes the attention grid).  Attention is a plain softmax over each sequence's own
+ * keys (MMDM_ATTN_NO_ZERO_KEY, no causal mask).  Every sequence's rows are BITWISE those of mmdm_encoder_layer_f32 on that sequence alone (nseq = 1,
+ * T = seq_len[s], causal = 0); rows outside every sequence are unspecified afterwards and influence nothing.
+ * Head sizes D / H = 64 and 128 (as mmdm_attention_ragged_opts_f32); any other head size, or norm_first != 0, is MMDM_ERR_UNSUPPORTED.
+ * workspace: mmdm_encoder_layer_workspace(1, total_rows, D, F) floats.
+ * Replaces MotionEncoder.transformer(h, src_key_padding_mask = a prefix mask)  src/evaluation/models.py:75. */
+int mmdm_encoder_layer_ragged_f32(float* x, const mmdm_encoder_layer_weights* w, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows,
+                                  int D, int H, int F, int norm_first, int activation, float eps, float* workspace, size_t workspace_floats, void* stream);
+
+/* The InterCLIP evaluator's row kernels (src/evaluation/models.py:57-74, 152, 178), in either build of the row kernels (build as in mmdm_layernorm_split).
+ * Item s of a batch is a TOKEN SEQUENCE of seq_len[s] rows -- the query token, then its first seq_len[s] - 1 frames -- at rows [seq_off[s], seq_off[s] +
+ * seq_len[s]) of a packed row space of total_rows rows (seq_off / seq_len: DEVICE ints [nseq], nseq <= 65535; max_len >= every length sizes the grid).
+ *   motion_pack:    the embedding GEMM's A operand [total_rows, lda] from motions [nseq, Tpad, npers * 262] (item_stride / row_stride in elements, npers 1 or
+ *                   2): A[seq_off[s] + 1 + t, p * 258 + j] = motions[s, t, p * 262 + j] for j < 258 (the last 4 features of every person are dropped),
+ *                   columns [npers * 258, Kp) and the token rows are zeros.  Frames t >= seq_len[s] - 1 are never read; max_len - 1 <= Tpad.
+ *   motion_tokens:  in place on the GEMM's output h [total_rows, D]: row seq_off[s] = query_token + pe[0], row seq_off[s] + 1 + t += pe[1 + t]
+ *                   (pe [pe_rows, D], pe_rows >= max_len rounded up to a multiple of 4; D % 4 == 0).
+ *   l2_normalize:   out[r] = x[r] / ||x[r]||_2 * scale[0] for x [rows, D] (scale: a DEVICE pointer -- the latent_scale parameter; D % 4 == 0, D <= 2048; in
+ *                   place allowed).  fp32 throughout; the sum of squares is reduced in a fixed order, so a row's bits do not depend on `rows`.
+ *                   mmdm_l2_normalize_rows_f32 is build 0.
+ * Rows outside every sequence are not written. */
+int mmdm_rowop_motion_pack(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, int lda, int Kp, int nseq,
+                           const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream);
+int mmdm_rowop_motion_tokens(float* h, const float* query_token, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len,
+                             int max_len, int total_rows, int build, void* stream);
+int mmdm_l2_normalize_rows_f32(const float* x, const float* scale, float* out, int rows, int D, void* stream);
+int mmdm_rowop_l2_normalize(const float* x, const float* scale, float* out, int rows, int D, int build, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2. The sampler handle: weights + workspace + captured step graph.
  * ---------------------------------------------------------------------------------------------- */

@@ -94,6 +94,11 @@ SYMBOLS = {
     "mmdm_gather_rows_f32": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "mmdm_encoder_layer_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "mmdm_encoder_layer_f32": (_I, [_VP, C.POINTER(EncoderLayerWeights), _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _VP, C.c_size_t, _VP]),
+    "mmdm_encoder_layer_ragged_f32": (_I, [_VP, C.POINTER(EncoderLayerWeights), _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, C.c_float, _VP, C.c_size_t, _VP]),
+    "mmdm_rowop_motion_pack": (_I, [_VP, C.c_int64, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP]),
+    "mmdm_rowop_motion_tokens": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP]),
+    "mmdm_l2_normalize_rows_f32": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
+    "mmdm_rowop_l2_normalize": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
     "mmdm_linear_fp8": (_I, [_VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP]),
     "mmdm_pack_weight_frag": (_I, [_VP, C.c_int64, _VP, _I, _I, _VP]),
     "mmdm_linear_bf16_packed": (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP]),

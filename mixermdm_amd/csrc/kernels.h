@@ -182,6 +182,16 @@ struct mmdm_rowops {
     int (*mdm_pack)(const float* src, const float* cond, int ldc, const float* time_tab, const int* step_idx, const float* pe, float* dst, void* planes,
                     int64_t plane_stride, const mmdm_rows& r, int gpp, int D, hipStream_t st);
     int (*mdm_unpack)(const float* src, float* dst, const mmdm_rows& r, int D, hipStream_t st);
+    // The InterCLIP motion encoder's sequence assembly on a ragged batch of token sequences (sequence s = rows [seq_off[s], seq_off[s] + seq_len[s]): the
+    // query token, then seq_len[s] - 1 frames; device arrays, max_len sizes the grid).  motion_pack: the embedding GEMM's A operand [total_rows, lda] from
+    // motions [nseq, Tpad, npers * 262] -- the last 4 features of every person dropped, columns [npers * 258, Kp) and the token rows zeros.
+    // motion_tokens: in place on the GEMM's output h [total_rows, D] -- token row = query + pe[0], frame row 1 + t += pe[1 + t].
+    int (*motion_pack)(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, int lda, int Kp, int nseq, const int* seq_off,
+                       const int* seq_len, int max_len, int total_rows, hipStream_t st);
+    int (*motion_tokens)(float* h, const float* query, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len, int max_len,
+                         int total_rows, hipStream_t st);
+    // out[r] = x[r] / ||x[r]||_2 * scale[0] (scale: device pointer)
+    int (*l2_normalize)(const float* x, const float* scale, float* out, int rows, int D, hipStream_t st);
 };
 extern const mmdm_rowops mmdm_rowops_tab, mmdm_rowops_tab_nopk;
 // Sequences of a RAGGED batch as the attention kernels see them (device arrays: one captured graph serves every batch of the same row bucket):

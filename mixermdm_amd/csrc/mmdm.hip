@@ -606,6 +606,7 @@ int linear(const Ctx& c, const float* A, int lda, const float* W, int ldw, const
 // the token sequences of a ragged MDM call -- the sum of their squared lengths and of their lengths (one token in front of every item's frames) come from its geometry
 int prof_begin_plain_attn(const Ctx& c, int nseq, int T, int H, int dh, bool tokens) {
     if (!tokens) return prof_begin(c, 1, 4.0 * nseq * H * (double)T * T * dh, 4.0 * nseq * H * dh * 4.0 * T);
+    if (!c.g) return MMDM_OK;                 // the stateless ragged layer (mmdm_encoder_layer_ragged_f32): no handle, no geometry, no profile
     const Geom& g = *c.g;
     return prof_begin(c, 1, 4.0 * (nseq / g.B) * H * dh * g.tok_tt, 4.0 * (nseq / g.B) * H * dh * 4.0 * ((double)g.real_rows + g.B));
 }
@@ -2104,6 +2105,18 @@ extern "C" size_t mmdm_encoder_layer_workspace(int nseq, int T, int D, int F) {
     return (size_t)nseq * T * ((size_t)5 * D + F);
 }
 
+// the caller's weight pointers (include/mmdm.h) as the stack's EncLayerW, for the two stateless encoder-layer entry points
+static int enc_layer_weights(const mmdm_encoder_layer_weights* w, EncLayerW& e, const char* who) {
+    for (const float* q : {w->in_proj_weight, w->in_proj_bias, w->out_proj_weight, w->out_proj_bias, w->linear1_weight, w->linear1_bias,
+                           w->linear2_weight, w->linear2_bias, w->norm1_weight, w->norm1_bias, w->norm2_weight, w->norm2_bias})
+        if (!q) return mmdm_set_error(MMDM_ERR_ARG, "%s: null weight pointer", who);
+    auto nc = [](const float* q) { return const_cast<float*>(q); };
+    e.in_w = nc(w->in_proj_weight); e.in_b = nc(w->in_proj_bias); e.out_w = nc(w->out_proj_weight); e.out_b = nc(w->out_proj_bias);
+    e.l1_w = nc(w->linear1_weight); e.l1_b = nc(w->linear1_bias); e.l2_w = nc(w->linear2_weight); e.l2_b = nc(w->linear2_bias);
+    e.n1_g = nc(w->norm1_weight); e.n1_b = nc(w->norm1_bias); e.n2_g = nc(w->norm2_weight); e.n2_b = nc(w->norm2_bias);
+    return MMDM_OK;
+}
+
 extern "C" int mmdm_encoder_layer_f32(float* x, const mmdm_encoder_layer_weights* w, int nseq, int T, int D, int H, int F, int norm_first,
                                       int activation, int causal, float eps, float* workspace, size_t workspace_floats, void* stream) {
     if (nseq == 0 || T == 0) return MMDM_OK;
@@ -2113,22 +2126,44 @@ extern "C" int mmdm_encoder_layer_f32(float* x, const mmdm_encoder_layer_weights
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_f32: activation must be MMDM_EPI_BIAS_GELU or MMDM_EPI_BIAS_QUICKGELU");
     if (workspace_floats < mmdm_encoder_layer_workspace(nseq, T, D, F))
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_f32: workspace too small (%zu < %zu floats)", workspace_floats, mmdm_encoder_layer_workspace(nseq, T, D, F));
-    for (const float* q : {w->in_proj_weight, w->in_proj_bias, w->out_proj_weight, w->out_proj_bias, w->linear1_weight, w->linear1_bias,
-                           w->linear2_weight, w->linear2_bias, w->norm1_weight, w->norm1_bias, w->norm2_weight, w->norm2_bias})
-        if (!q) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_f32: null weight pointer");
+    EncLayerW e;
+    RC(enc_layer_weights(w, e, "mmdm_encoder_layer_f32"));
     RC(mmdm_kernels_init());
     const size_t R = (size_t)nseq * T;
     float* qkv = workspace;
     float* att = qkv + R * 3 * D;
     float* tmp = att + R * D;
     float* f1 = tmp + R * D;
-    EncLayerW e;
-    auto nc = [](const float* q) { return const_cast<float*>(q); };
-    e.in_w = nc(w->in_proj_weight); e.in_b = nc(w->in_proj_bias); e.out_w = nc(w->out_proj_weight); e.out_b = nc(w->out_proj_bias);
-    e.l1_w = nc(w->linear1_weight); e.l1_b = nc(w->linear1_bias); e.l2_w = nc(w->linear2_weight); e.l2_b = nc(w->linear2_bias);
-    e.n1_g = nc(w->norm1_weight); e.n1_b = nc(w->norm1_bias); e.n2_g = nc(w->norm2_weight); e.n2_b = nc(w->norm2_bias);
     Ctx c{nullptr, static_cast<hipStream_t>(stream), nullptr};
     return encoder_layer(c, x, e, nseq, T, D, H, F, norm_first != 0, activation, causal != 0, eps, qkv, att, tmp, f1);
+}
+
+// The post-norm layer on a ragged batch: the public face of encoder_layer(..., rg).  The GEMMs and LayerNorms run on all total_rows rows (every instantiation
+// accumulates an output element in the same order and the row kernels are per row: a row's bits depend on nothing but the row), the attention walks the sequences.
+extern "C" int mmdm_encoder_layer_ragged_f32(float* x, const mmdm_encoder_layer_weights* w, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows,
+                                             int D, int H, int F, int norm_first, int activation, float eps, float* workspace, size_t workspace_floats, void* stream) {
+    if (nseq == 0 || total_rows == 0) return MMDM_OK;
+    if (!x || !w || !workspace || !seq_off || !seq_len || nseq < 0 || max_len <= 0 || total_rows < 0 || D <= 0 || H <= 0 || D % H || F <= 0)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_ragged_f32: bad arguments nseq=%d max_len=%d total_rows=%d D=%d H=%d F=%d", nseq, max_len, total_rows, D, H, F);
+    if (norm_first) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_encoder_layer_ragged_f32: norm_first is not supported on ragged batches (the post-norm form only)");
+    if (D / H != 64 && D / H != 128)
+        return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_encoder_layer_ragged_f32: head size %d is not supported on ragged batches (64 or 128)", D / H);
+    if (activation != MMDM_EPI_BIAS_GELU && activation != MMDM_EPI_BIAS_QUICKGELU)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_ragged_f32: activation must be MMDM_EPI_BIAS_GELU or MMDM_EPI_BIAS_QUICKGELU");
+    if (workspace_floats < mmdm_encoder_layer_workspace(1, total_rows, D, F))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_ragged_f32: workspace too small (%zu < %zu floats)", workspace_floats,
+                              mmdm_encoder_layer_workspace(1, total_rows, D, F));
+    EncLayerW e;
+    RC(enc_layer_weights(w, e, "mmdm_encoder_layer_ragged_f32"));
+    RC(mmdm_kernels_init());
+    const size_t R = (size_t)total_rows;
+    float* qkv = workspace;
+    float* att = qkv + R * 3 * D;
+    float* tmp = att + R * D;
+    float* f1 = tmp + R * D;
+    Ctx c{nullptr, static_cast<hipStream_t>(stream), nullptr};
+    const mmdm_rag_seq rg{seq_off, seq_len, total_rows, max_len};
+    return encoder_layer(c, x, e, nseq, max_len, D, H, F, false, activation, false, eps, qkv, att, tmp, f1, &rg);
 }
 
 extern "C" int mmdm_profile_enable(mmdm_handle h, int on) {

@@ -456,6 +456,76 @@ __global__ void gauss1d_kernel(const float* __restrict__ x, float* __restrict__ 
     out[idx] = (float)acc;
 }
 
+// InterCLIP's MotionEncoder (src/evaluation/models.py:57-66) on a RAGGED batch: item s is a token sequence of seq_len[s] rows -- the query token, then its
+// first seq_len[s] - 1 frames -- at rows [seq_off[s], seq_off[s] + seq_len[s]).  One wave per row: blockIdx.y = the item, wave blockIdx.x * 4 + w = the
+// position p inside it (the grid is sized by the longest item; waves past an item's end leave).
+// A[row, q * 258 + j] = motions[s, p - 1, q * 262 + j] for j < 258 (x.reshape(B, T, 2, -1)[..., :-4]); columns [npers * 258, Kp) and the token row are zeros.
+// Frames at and beyond seq_len[s] - 1 are never read.  A plain 4-byte loop: person 1 starts 1048 bytes into a motion row and 1032 bytes into an A row, so the
+// two sides share no 16-byte phase; consecutive lanes still read and write consecutive words.
+__global__ __launch_bounds__(256) void motion_pack_kernel(const float* __restrict__ motions, long long item_stride, int row_stride, int Tpad, int npers,
+                                                           float* __restrict__ A, int lda, int Kp, const int* __restrict__ seq_off,
+                                                           const int* __restrict__ seq_len, int total_rows) {
+    const int s = blockIdx.y, p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (p >= seq_len[s] || p > Tpad) return;                     // (wave-uniform)
+    const long long row = (long long)seq_off[s] + p;
+    if (row < 0 || row >= total_rows) return;
+    float* ap = A + (size_t)row * lda;
+    const int K = npers * (MMDM_NF - 4);
+    const float* mp = motions + (size_t)s * item_stride + (size_t)(p > 0 ? p - 1 : 0) * row_stride;
+    for (int c = lane; c < Kp; c += 64) {
+        float v = 0.f;
+        if (p > 0 && c < K) {
+            const int q = c / (MMDM_NF - 4);
+            v = mp[q * MMDM_NF + (c - q * (MMDM_NF - 4))];
+        }
+        ap[c] = v;
+    }
+}
+
+// In place on the embedding GEMM's output h [total_rows, D] (same row walk): the token row becomes query + pe[0], frame row p gets += pe[p]
+// (PositionalEncoding after the token is prepended: src/models/utils/utils.py:37-39).  D % 4 == 0, 16-byte rows.
+__global__ __launch_bounds__(256) void motion_tokens_kernel(float* __restrict__ h, const float* __restrict__ query, const float* __restrict__ pe, int D,
+                                                             const int* __restrict__ seq_off, const int* __restrict__ seq_len, int total_rows) {
+    const int s = blockIdx.y, p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (p >= seq_len[s]) return;                                 // (wave-uniform)
+    const long long row = (long long)seq_off[s] + p;
+    if (row < 0 || row >= total_rows) return;
+    float* hp = h + (size_t)row * D;
+    const float* pp = pe + (size_t)p * D;
+    for (int c = lane; c < (D >> 2); c += 64) {
+        const f32x4 e = *reinterpret_cast<const f32x4*>(pp + 4 * c);
+        const f32x4 a = p == 0 ? *reinterpret_cast<const f32x4*>(query + 4 * c) : *reinterpret_cast<const f32x4*>(hp + 4 * c);
+        *reinterpret_cast<f32x4*>(hp + 4 * c) = a + e;
+    }
+}
+
+// out[row] = x[row] / ||x[row]||_2 * scale[0]  (InterCLIP.encode_motion / encode_text: src/evaluation/models.py:152, 178).  One wave per row, the row in
+// registers; the sum of squares is a lane's own columns in ascending order, then the wave reduction: a row's bits do not depend on `rows`.  In place allowed.
+template <int MAXV>
+__global__ __launch_bounds__(256) void l2_normalize_kernel(const float* __restrict__ x, const float* __restrict__ scale, float* __restrict__ out, int rows, int D) {
+    const int lane = threadIdx.x & 63;
+    const int nv = D >> 2;
+    const float sc = scale[0];
+    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += gridDim.x * 4) {
+        const float* xp = x + (size_t)row * D;
+        f32x4 v[MAXV];
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (c < nv) v[i] = *reinterpret_cast<const f32x4*>(xp + 4 * c);
+            q += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
+        }
+        const float nrm = sqrtf(wave_sum(q));
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = lane + 64 * i;
+            if (c < nv) *reinterpret_cast<f32x4*>(out + (size_t)row * D + 4 * c) = v[i] / nrm * sc;
+        }
+    }
+}
+
 #ifdef MMDM_ROWOPS_NOPK
 }  // namespace nopk
 #endif
@@ -589,9 +659,58 @@ static int mean_time(const float* h, float* out, const mmdm_rows& r, int D, hipS
     return mmdm_check_launch("mean_time");
 }
 
+// the ragged token sequences of the two motion-encoder passes: device arrays, a grid of (positions of the longest sequence / 4, sequences)
+static int motion_seq_check(const char* who, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows) {
+    if (!seq_off || !seq_len || nseq < 0 || nseq > 65535 || max_len <= 0 || total_rows <= 0)
+        return mmdm_set_error(MMDM_ERR_ARG, "%s: bad sequence description nseq=%d (<= 65535) max_len=%d total_rows=%d", who, nseq, max_len, total_rows);
+    return MMDM_OK;
+}
+
+static int motion_pack(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, int lda, int Kp, int nseq, const int* seq_off,
+                       const int* seq_len, int max_len, int total_rows, hipStream_t st) {
+    if (nseq == 0) return MMDM_OK;
+    if (int rc = motion_seq_check("mmdm_rowop_motion_pack", nseq, seq_off, seq_len, max_len, total_rows)) return rc;
+    if (!motions || !A || npers < 1 || npers > 2 || Tpad < 0 || row_stride < npers * MMDM_NF || item_stride < (int64_t)Tpad * row_stride ||
+        Kp < npers * (MMDM_NF - 4) || lda < Kp)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_pack: bad arguments npers=%d Tpad=%d row stride=%d item stride=%lld Kp=%d lda=%d", npers, Tpad, row_stride,
+                              (long long)item_stride, Kp, lda);
+    if (max_len - 1 > Tpad) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_pack: max_len=%d sequences need %d frames, the buffer holds %d", max_len, max_len - 1, Tpad);
+    hipLaunchKernelGGL(motion_pack_kernel, dim3((max_len + 3) / 4, nseq), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, npers, A, lda, Kp, seq_off,
+                       seq_len, total_rows);
+    return mmdm_check_launch("motion_pack");
+}
+
+static int motion_tokens(float* h, const float* query, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len, int max_len,
+                         int total_rows, hipStream_t st) {
+    if (nseq == 0) return MMDM_OK;
+    if (int rc = motion_seq_check("mmdm_rowop_motion_tokens", nseq, seq_off, seq_len, max_len, total_rows)) return rc;
+    if (!h || !query || !pe || D <= 0 || pe_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens: bad arguments D=%d pe_rows=%d", D, pe_rows);
+    if ((D & 3) || ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(pe)) & 15))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens: D must be a multiple of 4 and pointers 16-byte aligned");
+    // the grid's positions are rounded up to whole blocks of 4 waves: every position a wave can take has a pe row
+    if ((max_len + 3) / 4 * 4 > pe_rows) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens: max_len=%d needs more than the %d pe rows", max_len, pe_rows);
+    hipLaunchKernelGGL(motion_tokens_kernel, dim3((max_len + 3) / 4, nseq), dim3(256), 0, st, h, query, pe, D, seq_off, seq_len, total_rows);
+    return mmdm_check_launch("motion_tokens");
+}
+
+static int l2_normalize(const float* x, const float* scale, float* out, int rows, int D, hipStream_t st) {
+    if (rows == 0) return MMDM_OK;
+    if (!x || !scale || !out || rows < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_l2_normalize_rows_f32: bad arguments rows=%d D=%d", rows, D);
+    if ((D & 3) || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) || (reinterpret_cast<uintptr_t>(scale) & 3))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_l2_normalize_rows_f32: D must be a multiple of 4 and x / out 16-byte aligned");
+    if (D > 64 * 4 * 8) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_l2_normalize_rows_f32: D=%d > 2048", D);
+    dim3 grid(min((rows + 3) / 4, 2048)), block(256);          // persistent wave slots, as layernorm
+    if (D <= 256) hipLaunchKernelGGL((l2_normalize_kernel<1>), grid, block, 0, st, x, scale, out, rows, D);
+    else if (D <= 512) hipLaunchKernelGGL((l2_normalize_kernel<2>), grid, block, 0, st, x, scale, out, rows, D);
+    else if (D <= 1024) hipLaunchKernelGGL((l2_normalize_kernel<4>), grid, block, 0, st, x, scale, out, rows, D);
+    else hipLaunchKernelGGL((l2_normalize_kernel<8>), grid, block, 0, st, x, scale, out, rows, D);
+    return mmdm_check_launch("l2_normalize");
+}
+
 // (host pass only: the device pass would emit a constant of external linkage too, and has no such functions to point at)
 #ifndef __HIP_DEVICE_COMPILE__
-const mmdm_rowops RO(mmdm_rowops_tab) = {adaln_any, layernorm, layernorm_planes, cond_silu, cond_silu_planes, mean_time, mdm_pack, mdm_unpack};
+const mmdm_rowops RO(mmdm_rowops_tab) = {adaln_any, layernorm,  layernorm_planes, cond_silu,     cond_silu_planes, mean_time,
+                                         mdm_pack,  mdm_unpack, motion_pack,      motion_tokens, l2_normalize};
 #endif
 
 #ifndef MMDM_ROWOPS_NOPK
@@ -744,4 +863,29 @@ extern "C" int mmdm_rowop_mdm_unpack_rag(const float* src, float* dst, int group
     return ro->mdm_unpack(src, dst, mmdm_rows{groups * B, 0, &fr, &tk}, D, static_cast<hipStream_t>(stream));
 }
 #undef ROWOP_RAG_CHECK
+
+// The InterCLIP evaluator's row operations (include/mmdm.h): argument checks are the launchers' own
+extern "C" int mmdm_rowop_motion_pack(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, int lda, int Kp, int nseq,
+                                      const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream) {
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_motion_pack");
+    if (!ro) return MMDM_ERR_ARG;
+    return ro->motion_pack(motions, item_stride, row_stride, Tpad, npers, A, lda, Kp, nseq, seq_off, seq_len, max_len, total_rows, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmdm_rowop_motion_tokens(float* h, const float* query_token, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len,
+                                        int max_len, int total_rows, int build, void* stream) {
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_motion_tokens");
+    if (!ro) return MMDM_ERR_ARG;
+    return ro->motion_tokens(h, query_token, pe, pe_rows, D, nseq, seq_off, seq_len, max_len, total_rows, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmdm_l2_normalize_rows_f32(const float* x, const float* scale, float* out, int rows, int D, void* stream) {
+    return l2_normalize(x, scale, out, rows, D, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmdm_rowop_l2_normalize(const float* x, const float* scale, float* out, int rows, int D, int build, void* stream) {
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_l2_normalize");
+    if (!ro) return MMDM_ERR_ARG;
+    return ro->l2_normalize(x, scale, out, rows, D, static_cast<hipStream_t>(stream));
+}
 #endif

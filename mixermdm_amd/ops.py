@@ -188,6 +188,81 @@ def encoder_layer_(x, w, num_heads, norm_first=False, activation="gelu", causal=
     return x
 
 
+def _seq_args(seq_off, seq_len):
+    _chk(seq_off, seq_len)
+    assert seq_off.dtype == torch.int32 and seq_len.dtype == torch.int32 and seq_off.is_contiguous() and seq_len.is_contiguous()
+    assert seq_off.dim() == 1 and seq_off.numel() == seq_len.numel()
+    return seq_off.numel(), _p(seq_off), _p(seq_len)
+
+
+def encoder_layer_ragged_(x, w, num_heads, seq_off, seq_len, max_len, norm_first=False, activation="gelu", eps=1e-5, workspace=None):
+    """One post-norm nn.TransformerEncoderLayer on a ragged batch, x [total_rows, D] IN PLACE (mmdm_encoder_layer_ragged_f32): sequence s = rows
+    [seq_off[s], seq_off[s] + seq_len[s]) (int32 device tensors), plain softmax over its own keys; max_len >= every length.  Every sequence's rows are
+    bitwise those of encoder_layer_ on that sequence alone.  w as in encoder_layer_.  Head sizes 64 / 128; norm_first is refused by the library."""
+    names = ("in_proj_weight", "in_proj_bias", "out_proj.weight", "out_proj.bias", "linear1.weight", "linear1.bias",
+             "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
+    ts = [w[k] for k in names]
+    _chk(x, *ts)
+    assert x.dim() == 2 and x.is_contiguous() and all(t.is_contiguous() for t in ts)
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    rows, D = x.shape
+    F = w["linear1.weight"].shape[0]
+    lib = load_library()
+    need = lib.mmdm_encoder_layer_workspace(1, rows, D, F)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=x.device, dtype=torch.float32)
+    cw = EncoderLayerWeights(*[t.data_ptr() for t in ts])
+    check(lib.mmdm_encoder_layer_ragged_f32(_p(x), C.byref(cw), nseq, po, pl, int(max_len), rows, D, num_heads, F, int(norm_first), EPI[activation], float(eps),
+                                            _p(workspace), workspace.numel(), _stream()))
+    return x
+
+
+def motion_pack(motions, seq_off, seq_len, max_len, total_rows, npers=2, k_pad=None, build=0, out=None):
+    """The InterCLIP motion encoder's embedding operand (mmdm_rowop_motion_pack): motions [B, Tpad, npers * 262] (last-dim stride 1) -> A [total_rows, k_pad]
+    with frame t of item s at row seq_off[s] + 1 + t, the last 4 features of every person dropped, the columns from npers * 258 on and the token rows
+    (seq_off[s]) zeros.  Item s is seq_len[s] rows: its token and its first seq_len[s] - 1 frames; frames beyond are never read.  k_pad: npers * 258
+    rounded up to a multiple of 16 unless given.  Rows outside every sequence are left as they are in `out` (a new tensor: uninitialised).  build as in
+    `adaln`."""
+    _chk(motions)
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    assert motions.dim() == 3 and motions.stride(2) == 1 and motions.shape[0] == nseq and motions.shape[2] == npers * 262
+    K = npers * 258
+    k_pad = (K + 15) // 16 * 16 if k_pad is None else int(k_pad)
+    if out is None:
+        out = torch.empty(total_rows, k_pad, device=motions.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= total_rows and out.shape[1] == k_pad
+    check(load_library().mmdm_rowop_motion_pack(_p(motions), motions.stride(0), motions.stride(1), motions.shape[1], int(npers), _p(out), out.stride(0), k_pad,
+                                                nseq, po, pl, int(max_len), int(total_rows), int(build), _stream()))
+    return out
+
+
+def motion_tokens_(h, query_token, pe, seq_off, seq_len, max_len, build=0):
+    """IN PLACE on the embedding GEMM's output h [total_rows, D] (mmdm_rowop_motion_tokens): row seq_off[s] = query_token + pe[0], row seq_off[s] + 1 + t
+    += pe[1 + t].  query_token [D] or [1, D], pe [rows, D] contiguous.  build as in `adaln`."""
+    _chk(h, query_token, pe)
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    assert h.dim() == 2 and h.is_contiguous() and pe.dim() == 2 and pe.is_contiguous() and query_token.is_contiguous()
+    rows, D = h.shape
+    assert pe.shape[1] == D and query_token.numel() == D
+    check(load_library().mmdm_rowop_motion_tokens(_p(h), _p(query_token), _p(pe), pe.shape[0], D, nseq, po, pl, int(max_len), rows, int(build), _stream()))
+    return h
+
+
+def l2_normalize(x, scale, build=0):
+    """x / ||x||_2 * scale over the last dimension (mmdm_l2_normalize_rows_f32); scale: a one-element fp32 DEVICE tensor (InterCLIP's latent_scale).
+    build as in `adaln`."""
+    _chk(x, scale)
+    assert scale.numel() == 1
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    D = x.shape[-1]
+    if build == 0:
+        check(load_library().mmdm_l2_normalize_rows_f32(_p(x), _p(scale), _p(out), x.numel() // D, D, _stream()))
+    else:
+        check(load_library().mmdm_rowop_l2_normalize(_p(x), _p(scale), _p(out), x.numel() // D, D, int(build), _stream()))
+    return out
+
+
 def cond_silu(time_tab, step_idx, txt, build=0, planes=False, out=None):
     """silu(time_tab[*step_idx] + txt) for txt [rows, D].  build as in `adaln`.  planes: the values as their two fp16 planes instead (float16; `out`, if
     given, is a contiguous float16 tensor [2, n >= rows * D] whose row length n is the plane stride)."""
