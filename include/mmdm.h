@@ -406,6 +406,26 @@ int mmdm_rowop_motion_tokens(float* h, const float* query_token, const float* pe
 int mmdm_l2_normalize_rows_f32(const float* x, const float* scale, float* out, int rows, int D, void* stream);
 int mmdm_rowop_l2_normalize(const float* x, const float* scale, float* out, int rows, int D, int build, void* stream);
 
+/* Centring of the InterCLIP INDIVIDUAL evaluator (EvaluatorModelWrapperIndividual  src/evaluation/utils.py:284-288; center_motion  src/utils/alignment.py:
+ * 161-222): every person of every item of motions [nitems, Tpad, npers * 262] (item_stride / row_stride in elements) is centred on its own,
+ *   center_motion: out[i, t, p * 262 + c] = smpl_to_ih(center_motion(ih_to_smpl(motions[i, :, p * 262 : (p + 1) * 262])))[t, c] for ALL Tpad frames; npers 1 or 2;
+ *                  channels 258..261 of every person come out exactly 0.  The output must not overlap the input (MMDM_ERR_ARG).
+ *   center_pack:   two persons.  Sequence s = 2 * i + p is person p of item i, a token sequence as in mmdm_rowop_motion_pack (nseq = 2 * nitems <= 65535):
+ *                  row seq_off[s] and columns [258, Kp) are zeros, row seq_off[s] + 1 + t holds the first 258 centred channels of frame t for
+ *                  t < seq_len[s] - 1 -- BITWISE the A operand mmdm_rowop_motion_pack(npers = 1) makes of center_motion's output viewed as
+ *                  [2 * nitems, Tpad, 262].  Frames at and beyond a length are never transformed or written (their position Y is read: the floor), rows
+ *                  outside every sequence are not touched.  Kp >= 258, lda >= Kp, max_len - 1 <= Tpad.
+ * The reference's contract, kept: the floor is the minimum of position Y over ALL Tpad frames handed in x 22 joints, NOT over the item's length (the
+ * reference centres the padded buffer before it slices it: a zero-padded tail contributes 0); frame 0 supplies the root XZ and the hip-across vector
+ * (joints 2, 1); the facing rotation is qbetween(normalize(cross(Y, across)), +Z), the cross product along the last dimension for every batch size (the
+ * reference's torch.cross without dim goes wrong at a per-call batch of exactly 3: not reproduced).  A NaN position Y is dropped by the minimum where
+ * torch.min would propagate it, and coincident hips divide by zero as in the reference: neither is pinned.
+ * floor_ws: [nitems * npers] floats of the caller's (center_pack: [nitems * 2]); nothing is allocated inside the call. */
+int mmdm_center_motion_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, int npers, float* out, int64_t out_item_stride,
+                           int out_row_stride, float* floor_ws, void* stream);
+int mmdm_center_pack_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, float* A, int lda, int Kp, const int* seq_off,
+                         const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2. The sampler handle: weights + workspace + captured step graph.
  * ---------------------------------------------------------------------------------------------- */

@@ -99,6 +99,8 @@ SYMBOLS = {
     "mmdm_rowop_motion_tokens": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP]),
     "mmdm_l2_normalize_rows_f32": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "mmdm_rowop_l2_normalize": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
+    "mmdm_center_motion_f32": (_I, [_VP, C.c_int64, _I, _I, _I, _I, _VP, C.c_int64, _I, _VP, _VP]),
+    "mmdm_center_pack_f32": (_I, [_VP, C.c_int64, _I, _I, _I, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP]),
     "mmdm_linear_fp8": (_I, [_VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP]),
     "mmdm_pack_weight_frag": (_I, [_VP, C.c_int64, _VP, _I, _I, _VP]),
     "mmdm_linear_bf16_packed": (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP]),

@@ -275,6 +275,35 @@ __global__ __launch_bounds__(256) void floor_kernel(const float* __restrict__ m,
     if (threadIdx.x == 0) floor_ws[bp] = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
 }
 
+// smpl_to_ih(center_motion(ih_to_smpl(.)))  alignment.py:161-222 for the channels ONE thread owns (joint j of one frame of one person): raw / v1 hold
+// pos j (3), vel j (3), then rot j (6, j < 21) or the feet (4, j == 21).  fl: the person's floor (floor_kernel / center_floor_kernel); f0: the person's
+// frame 0, which supplies the root XZ and the hip-across vector.  Positions / velocities are unchanged by ih_to_smpl; the facing rotation is
+// qbetween(normalize(cross(Y, across)), +Z) with the cross product along the last dimension.  One definition for the DDIM update and the evaluator's
+// two centring kernels: the operation order is the update kernel's, value for value.
+struct Centred { V3 pos, vel; float rot[6]; };          // rot: the rot6d of joint j < 21; zeros for j == 21 (the feet)
+__device__ __forceinline__ Centred center_channels(float fl, const float* f0, int j, V3 pos, V3 vel, const float (&d)[6]) {
+    const V3 root{f0[0], f0[1] - fl, f0[2]};
+    const V3 rh{f0[3 * R_HIP], f0[3 * R_HIP + 1] - fl, f0[3 * R_HIP + 2]};
+    const V3 lhp{f0[3 * L_HIP], f0[3 * L_HIP + 1] - fl, f0[3 * L_HIP + 2]};
+    V3 ac{rh.x - lhp.x, rh.y - lhp.y, rh.z - lhp.z};
+    const float an = sqrtf(ac.x * ac.x + ac.y * ac.y + ac.z * ac.z);
+    ac = V3{ac.x / an, ac.y / an, ac.z / an};
+    V3 fw = cross3(V3{0.f, 1.f, 0.f}, ac);
+    const float fn = sqrtf(fw.x * fw.x + fw.y * fw.y + fw.z * fw.z);
+    fw = V3{fw.x / fn, fw.y / fn, fw.z / fn};
+    const Q4 q = qbetween(fw, V3{0.f, 0.f, 1.f});
+    const V3 xz{root.x * 1.f, root.y * 0.f, root.z * 1.f};
+    Centred c;
+    c.pos = qrot(q, V3{pos.x - xz.x, (pos.y - fl) - xz.y, pos.z - xz.z});
+    c.vel = qrot(q, vel);
+    if (j < 21) rot6d_roundtrip(d, c.rot);
+    else {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) c.rot[k] = 0.f;
+    }
+    return c;
+}
+
 __device__ __forceinline__ float ddim(float x, float x0, float c0, float c1, float c2, float c3) {
     const float eps = (c0 * x - x0) / c1;        // _predict_eps_from_xstart  gaussian_diffusion.py:558-562
     return x0 * c2 + c3 * eps;                   // eta = 0 mean             :1949-1956
@@ -399,35 +428,14 @@ __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restric
     for (int k = 0; k < 12; ++k) { raw[k] = (k < nch) ? mo[ch[k]] : 0.f; v1[k] = raw[k]; }
 
     if (norm && align) {
-        // center_motion  alignment.py:161-222 on the ih_to_smpl'ed motion (positions / velocities unchanged by ih_to_smpl)
-        const float fl = floor_ws[b * 2 + p];
-        const float* f0 = m + seq;                                // frame 0
-        const V3 root{f0[0], f0[1] - fl, f0[2]};
-        const V3 rh{f0[3 * R_HIP], f0[3 * R_HIP + 1] - fl, f0[3 * R_HIP + 2]};
-        const V3 lhp{f0[3 * L_HIP], f0[3 * L_HIP + 1] - fl, f0[3 * L_HIP + 2]};
-        V3 ac{rh.x - lhp.x, rh.y - lhp.y, rh.z - lhp.z};
-        const float an = sqrtf(ac.x * ac.x + ac.y * ac.y + ac.z * ac.z);
-        ac = V3{ac.x / an, ac.y / an, ac.z / an};
-        V3 fw = cross3(V3{0.f, 1.f, 0.f}, ac);
-        const float fn = sqrtf(fw.x * fw.x + fw.y * fw.y + fw.z * fw.z);
-        fw = V3{fw.x / fn, fw.y / fn, fw.z / fn};
-        const Q4 q = qbetween(fw, V3{0.f, 0.f, 1.f});
-        const V3 xz{root.x * 1.f, root.y * 0.f, root.z * 1.f};
-        const V3 pc = qrot(q, V3{raw[0] - xz.x, (raw[1] - fl) - xz.y, raw[2] - xz.z});
-        const V3 vc = qrot(q, V3{raw[3], raw[4], raw[5]});
-        v1[0] = pc.x; v1[1] = pc.y; v1[2] = pc.z;
-        v1[3] = vc.x; v1[4] = vc.y; v1[5] = vc.z;
-        if (j < 21) {
-            float d[6], r[6];
+        float d[6];
 #pragma unroll
-            for (int k = 0; k < 6; ++k) d[k] = raw[6 + k];
-            rot6d_roundtrip(d, r);
+        for (int k = 0; k < 6; ++k) d[k] = raw[6 + k];
+        const Centred c = center_channels(floor_ws[b * 2 + p], m + seq, j, V3{raw[0], raw[1], raw[2]}, V3{raw[3], raw[4], raw[5]}, d);
+        v1[0] = c.pos.x; v1[1] = c.pos.y; v1[2] = c.pos.z;
+        v1[3] = c.vel.x; v1[4] = c.vel.y; v1[5] = c.vel.z;
 #pragma unroll
-            for (int k = 0; k < 6; ++k) v1[6 + k] = r[k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v1[6 + k] = 0.f;
-        }
+        for (int k = 0; k < 6; ++k) v1[6 + k] = c.rot[k];
     }
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
@@ -456,6 +464,102 @@ __global__ __launch_bounds__(256) void xstart_ddim_kernel(const float* __restric
         }
         if (px1) px1[e] = x0a;
         if (px2) px2[e] = x0b;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Centring of the InterCLIP individual evaluator (EvaluatorModelWrapperIndividual, src/evaluation/utils.py:284-288): every person of every item becomes
+// smpl_to_ih(center_motion(ih_to_smpl(person))) before it is encoded as a motion of its own.  motions [nitems, Tpad, npers * 262] with element strides.
+// CONTRACT (the reference's, kept):
+//   * the floor is the minimum of position Y over ALL Tpad frames handed in x 22 joints, not over the item's length: the reference centres the padded
+//     buffer before it slices to the longest length, so a zero-padded tail contributes 0 to the minimum;
+//   * frame 0 supplies the root XZ and the hip-across vector (joints 2, 1); the facing rotation is qbetween(normalize(cross(Y, across)), +Z);
+//   * the cross product runs along the last dimension for EVERY batch size (the reference's torch.cross without dim goes wrong at a per-call batch of
+//     exactly 3, SURVEY quirk 9: not reproduced);
+//   * channels 258..261 of every person come out 0.
+// Not pinned: fminf drops a NaN where torch.min propagates it; coincident hips divide by zero here as they do in the reference.
+// Launch shape: a block per (item, person) for the floor, then one thread per (item, person, frame, joint) as in the update kernel -- HBM-bound, the
+// 21 rotation round trips of a frame spread over lanes.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void center_floor_kernel(const float* __restrict__ m, long long item_stride, int row_stride, int Tpad, int npers,
+                                                            float* __restrict__ floor_ws) {
+    const int ip = blockIdx.x;                   // item * npers + person
+    const float* base = m + (size_t)(ip / npers) * item_stride + (size_t)(ip % npers) * NF;
+    float v = INFINITY;
+    for (int i = threadIdx.x; i < Tpad * NJ; i += blockDim.x) {
+        const int t = i / NJ, j = i % NJ;
+        v = fminf(v, base[(size_t)t * row_stride + 3 * j + 1]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) floor_ws[ip] = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+}
+
+// joint j of frame `mo` (the person's 262 features of that frame) centred; the feet are not read: they come out 0 whatever they hold
+__device__ __forceinline__ Centred center_joint(float fl, const float* f0, const float* __restrict__ mo, int j) {
+    float d[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d[k] = j < 21 ? mo[ROT0 + 6 * j + k] : 0.f;
+    return center_channels(fl, f0, j, V3{mo[3 * j], mo[3 * j + 1], mo[3 * j + 2]}, V3{mo[66 + 3 * j], mo[66 + 3 * j + 1], mo[66 + 3 * j + 2]}, d);
+}
+
+// out[i, t, p * 262 + c] for all Tpad frames; one thread per (item, person, frame, joint)
+__global__ __launch_bounds__(256) void center_motion_kernel(const float* __restrict__ m, long long item_stride, int row_stride, int Tpad, int npers,
+                                                             long long total, float* __restrict__ out, long long out_item_stride, int out_row_stride,
+                                                             const float* __restrict__ floor_ws) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int j = (int)(idx % NJ);
+    long long r = idx / NJ;
+    const int t = (int)(r % Tpad);
+    r /= Tpad;
+    const int p = (int)(r % npers);
+    const long long i = r / npers;
+    const float* pb = m + (size_t)i * item_stride + (size_t)p * NF;          // frame 0 of the person
+    const Centred c = center_joint(floor_ws[i * npers + p], pb, pb + (size_t)t * row_stride, j);
+    float* o = out + (size_t)i * out_item_stride + (size_t)t * out_row_stride + (size_t)p * NF;
+    o[3 * j] = c.pos.x; o[3 * j + 1] = c.pos.y; o[3 * j + 2] = c.pos.z;
+    o[66 + 3 * j] = c.vel.x; o[66 + 3 * j + 1] = c.vel.y; o[66 + 3 * j + 2] = c.vel.z;
+    if (j < 21) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o[ROT0 + 6 * j + k] = c.rot[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[FEET0 + k] = c.rot[k];
+    }
+}
+
+// The same values written straight into the embedding GEMM's A operand of the ragged motion encoder (rowops.hip motion_pack_kernel with npers = 1 on the
+// centred motion): sequence s = 2 * item + person owns rows [seq_off[s], seq_off[s] + seq_len[s]) -- the token row (zeros), then its first
+// seq_len[s] - 1 frames, 258 centred channels each, columns [258, Kp) zeros.  32 threads per row, 8 rows per block: lanes 0..21 are the joints, the other
+// ten write the zero columns.  Frames at and beyond the length are never transformed or written (only their position Y is read, by the floor); rows
+// outside every sequence are not touched.
+__global__ __launch_bounds__(256) void center_pack_kernel(const float* __restrict__ m, long long item_stride, int row_stride, int Tpad,
+                                                           float* __restrict__ A, int lda, int Kp, const int* __restrict__ seq_off,
+                                                           const int* __restrict__ seq_len, int total_rows, const float* __restrict__ floor_ws) {
+    const int s = blockIdx.y, pos = blockIdx.x * 8 + (threadIdx.x >> 5), l = threadIdx.x & 31;
+    if (pos >= seq_len[s] || pos > Tpad) return;
+    const long long row = (long long)seq_off[s] + pos;
+    if (row < 0 || row >= total_rows) return;
+    float* ap = A + (size_t)row * lda;
+    if (pos == 0) {
+        for (int c = l; c < Kp; c += 32) ap[c] = 0.f;
+        return;
+    }
+    if (l >= NJ) {
+        for (int c = FEET0 + (l - NJ); c < Kp; c += 32 - NJ) ap[c] = 0.f;
+        return;
+    }
+    const float* pb = m + (size_t)(s >> 1) * item_stride + (size_t)(s & 1) * NF;
+    const Centred c = center_joint(floor_ws[s], pb, pb + (size_t)(pos - 1) * row_stride, l);
+    ap[3 * l] = c.pos.x; ap[3 * l + 1] = c.pos.y; ap[3 * l + 2] = c.pos.z;
+    ap[66 + 3 * l] = c.vel.x; ap[66 + 3 * l + 1] = c.vel.y; ap[66 + 3 * l + 2] = c.vel.z;
+    if (l < 21) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ap[ROT0 + 6 * l + k] = c.rot[k];
     }
 }
 
@@ -775,6 +879,51 @@ extern "C" int mmdm_xstart_ddim_f32(const float* model_out, const float* stats, 
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_xstart_ddim_f32: bad arguments");
     return mmdm_xstart_ddim(0, model_out, stats, coef, nullptr, S, step_idx, nullptr, nullptr, x, x2, pred_xstart, pred_xstart2, floor_ws, mmdm_rows{B, T}, align,
                             static_cast<hipStream_t>(stream));
+}
+
+// what the two centring entries ask of their motions argument
+static int center_args_check(const char* who, const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, int npers, const float* floor_ws) {
+    if (!motions || !floor_ws || nitems < 0 || npers < 1 || npers > 2 || Tpad < 0 || Tpad > (1 << 24) || row_stride < npers * MMDM_NF ||
+        item_stride < (int64_t)Tpad * row_stride)
+        return mmdm_set_error(MMDM_ERR_ARG, "%s: bad arguments nitems=%d npers=%d Tpad=%d row stride=%d item stride=%lld", who, nitems, npers, Tpad, row_stride,
+                              (long long)item_stride);
+    return MMDM_OK;
+}
+
+extern "C" int mmdm_center_motion_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, int npers, float* out,
+                                      int64_t out_item_stride, int out_row_stride, float* floor_ws, void* stream) {
+    if (nitems == 0 || Tpad == 0) return MMDM_OK;
+    if (int rc = center_args_check("mmdm_center_motion_f32", motions, item_stride, row_stride, Tpad, nitems, npers, floor_ws)) return rc;
+    if (!out || out_row_stride < npers * MMDM_NF || out_item_stride < (int64_t)Tpad * out_row_stride)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_motion_f32: bad output row stride=%d item stride=%lld", out_row_stride, (long long)out_item_stride);
+    if (out < motions + (int64_t)nitems * item_stride && motions < out + (int64_t)nitems * out_item_stride)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_motion_f32: the output must not alias the input (every frame reads frame 0 and the floor of its item)");
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(center_floor_kernel, dim3(nitems * npers), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, npers, floor_ws);
+    if (int rc = mmdm_check_launch("center_floor")) return rc;
+    const long long total = (long long)nitems * npers * Tpad * MMDM_NJ;
+    if ((total + 255) / 256 > 0x7fffffffLL) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_motion_f32: %d items of %d frames exceed one launch", nitems, Tpad);
+    hipLaunchKernelGGL(center_motion_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, npers, total,
+                       out, (long long)out_item_stride, out_row_stride, floor_ws);
+    return mmdm_check_launch("center_motion");
+}
+
+extern "C" int mmdm_center_pack_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, float* A, int lda, int Kp,
+                                    const int* seq_off, const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream) {
+    if (nitems == 0) return MMDM_OK;
+    if (int rc = center_args_check("mmdm_center_pack_f32", motions, item_stride, row_stride, Tpad, nitems, 2, floor_ws)) return rc;
+    // the sequence description of mmdm_rowop_motion_pack, two sequences per item
+    if (!seq_off || !seq_len || 2 * (int64_t)nitems > 65535 || max_len <= 0 || total_rows <= 0)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_pack_f32: bad sequence description nseq=%lld (<= 65535) max_len=%d total_rows=%d", 2 * (long long)nitems, max_len,
+                              total_rows);
+    if (!A || Kp < MMDM_NF - 4 || lda < Kp) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_pack_f32: bad operand Kp=%d lda=%d", Kp, lda);
+    if (max_len - 1 > Tpad) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_pack_f32: max_len=%d sequences need %d frames, the buffer holds %d", max_len, max_len - 1, Tpad);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(center_floor_kernel, dim3(nitems * 2), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, 2, floor_ws);
+    if (int rc = mmdm_check_launch("center_floor")) return rc;
+    hipLaunchKernelGGL(center_pack_kernel, dim3((max_len + 7) / 8, nitems * 2), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, A, lda, Kp, seq_off,
+                       seq_len, total_rows, floor_ws);
+    return mmdm_check_launch("center_pack");
 }
 
 int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rows& r, hipStream_t st) {

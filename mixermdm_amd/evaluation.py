@@ -14,6 +14,11 @@ are 32 x 32 and 512 x 512.
 Order convention (the reference's docstring: "the results does not following the order of inputs"): ``get_co_embeddings`` returns both
 embeddings in the order ``np.argsort(motion_lens.tolist())[::-1]`` -- longest motion first, computed with numpy on the host exactly so.
 
+The individual half of the reference's table (EvaluatorModelWrapperIndividual  src/evaluation/utils.py:237-383; calculate_f_score
+src/scripts/eval/mixermdm.py:117-121, 216-241): every person of an interaction is centred on its own and encoded by an InterCLIP in MODE: individual
+-- ``InterCLIP.encode_motion_individual`` over the fused centre-and-pack kernel (``ops.center_pack``), 2B embeddings in the order p1 of item 0, p2 of
+item 0, ..., no length sort -- and ``summarize_replications`` / ``f_score_summary`` give the mean, the confidence interval and the harmonic mean.
+
 Bitwise: an item's motion embedding does not depend on the batch it is encoded in, on its position in it, or on what the buffer holds beyond
 its length (the reference's own batched result differs from its alone result in the last bits).
 """
@@ -136,21 +141,18 @@ class InterCLIP:
         seq_off = np.concatenate([[0], np.cumsum(seq_len)[:-1]]).astype(np.int32)
         return seq_off, seq_len, int(seq_len.sum()), int(seq_len.max())
 
-    def encode_motion(self, batch):
-        """batch["motions"] [B, T, npers * 262], batch["motion_lens"] [B] -> batch["motion_emb"] [B, 512] (models.py:144-154, 50-80)."""
-        w = self._weights()
+    def _motion_args(self, batch, who, width):
+        """The checked inputs of an encode_motion call: (motions fp32 on the device [B, T, width], the batch's sequence layout on the host)."""
         motions = torch.as_tensor(batch["motions"]).to(device=self.device, dtype=torch.float32)
-        if motions.dim() != 3 or motions.shape[2] != self.npers * NFEATS:
-            raise ValueError(f"encode_motion: motions [B, T, {self.npers * NFEATS}] expected, got {tuple(motions.shape)}")
+        if motions.dim() != 3 or motions.shape[2] != width:
+            raise ValueError(f"{who}: motions [B, T, {width}] expected, got {tuple(motions.shape)}")
         if motions.stride(2) != 1:
             motions = motions.contiguous()
-        B, T, _ = motions.shape
-        off_h, len_h, total, longest = self.sequence_layout(T, batch["motion_lens"])
-        if len(off_h) != B:
-            raise ValueError(f"encode_motion: {B} motions but {len(off_h)} lengths")
-        seq_off = torch.from_numpy(off_h).to(self.device)
-        seq_len = torch.from_numpy(len_h).to(self.device)
-        a = ops.motion_pack(motions, seq_off, seq_len, longest, total, npers=self.npers, k_pad=self.k_pad)
+        return motions, self.sequence_layout(motions.shape[1], batch["motion_lens"])
+
+    def _encode_packed(self, a, seq_off, seq_len, total, longest):
+        """From the embedding GEMM's A operand [total, k_pad] of packed token sequences to their embeddings [nseq, 512]."""
+        w = self._weights()
         h = ops.linear(a, w["embed_w"], w["embed_b"])
         ops.motion_tokens_(h, w["query"], w["pe"], seq_off, seq_len, longest)
         ws = torch.empty(ops.load_library().mmdm_encoder_layer_workspace(1, total, self.D, self.F), device=self.device, dtype=torch.float32)
@@ -159,7 +161,40 @@ class InterCLIP:
         tok = ops.gather_rows(h, seq_off)
         tok = ops.layernorm(tok, w["out_ln_w"], w["out_ln_b"], 1e-5)
         emb = ops.linear(tok, w["m_out_w"], w["m_out_b"])
-        batch["motion_emb"] = ops.l2_normalize(emb, w["scale"])
+        return ops.l2_normalize(emb, w["scale"])
+
+    def encode_motion(self, batch):
+        """batch["motions"] [B, T, npers * 262], batch["motion_lens"] [B] -> batch["motion_emb"] [B, 512] (models.py:144-154, 50-80)."""
+        self._weights()
+        motions, (off_h, len_h, total, longest) = self._motion_args(batch, "encode_motion", self.npers * NFEATS)
+        if len(off_h) != motions.shape[0]:
+            raise ValueError(f"encode_motion: {motions.shape[0]} motions but {len(off_h)} lengths")
+        seq_off = torch.from_numpy(off_h).to(self.device)
+        seq_len = torch.from_numpy(len_h).to(self.device)
+        a = ops.motion_pack(motions, seq_off, seq_len, longest, total, npers=self.npers, k_pad=self.k_pad)
+        batch["motion_emb"] = self._encode_packed(a, seq_off, seq_len, total, longest)
+        return batch
+
+    def encode_motion_individual(self, batch):
+        """MODE: individual only.  batch["motions"] [B, T, 524] (both persons of an interaction), batch["motion_lens"] [B] -> batch["motion_emb"] [2B, 512] in
+        the order p1 of item 0, p2 of item 0, p1 of item 1, ... -- what EvaluatorModelWrapperIndividual (src/evaluation/utils.py:284-315) hands its encoder:
+        every person centred on its own with smpl_to_ih(center_motion(ih_to_smpl(.))) over the WHOLE buffer handed in (the floor is the minimum over all T
+        frames, padding included: ops.center_motion), interleaved at batch level, lengths repeated.  Centring and packing are one pass (ops.center_pack); the
+        padded [2B, T, 262] tensor is never formed.  The cross product of the facing runs along the last dimension for every B (the reference's
+        torch.cross without dim goes wrong at a per-call batch of exactly 3: not reproduced)."""
+        if self.mode != "individual":
+            raise ValueError(f"encode_motion_individual: the model's MODE is {self.mode!r}; the per-person encoding needs MODE 'individual'")
+        self._weights()
+        motions, (off_h, len_h, _, longest) = self._motion_args(batch, "encode_motion_individual", 2 * NFEATS)
+        if len(off_h) != motions.shape[0]:
+            raise ValueError(f"encode_motion_individual: {motions.shape[0]} motions but {len(off_h)} lengths")
+        len_h = np.repeat(len_h, 2)
+        off_h = np.concatenate([[0], np.cumsum(len_h)[:-1]]).astype(np.int32)
+        total = int(len_h.sum())
+        seq_off = torch.from_numpy(off_h).to(self.device)
+        seq_len = torch.from_numpy(len_h).to(self.device)
+        a = ops.center_pack(motions, seq_off, seq_len, longest, total, k_pad=self.k_pad)
+        batch["motion_emb"] = self._encode_packed(a, seq_off, seq_len, total, longest)
         return batch
 
     # ---- text --------------------------------------------------------------------------------------------------------------------------
@@ -224,6 +259,58 @@ class EvaluatorModelWrapper:
         with torch.no_grad():
             batch, _ = self._batch(batch_data)
             return self.model.encode_motion(batch)["motion_emb"]
+
+
+class EvaluatorModelWrapperIndividual:
+    """EvaluatorModelWrapperIndividual of src/evaluation/utils.py:237-383: every person of an interaction is scored as a motion of its own against its own
+    prompt by an InterCLIP in MODE: individual.  cfg_or_model as in EvaluatorModelWrapper.  No length sort: embeddings come in the order p1 of item 0,
+    p2 of item 0, p1 of item 1, ...; the centring is InterCLIP.encode_motion_individual's (over the whole buffer handed in)."""
+    individual = True
+
+    def __init__(self, cfg_or_model, device="cuda"):
+        if isinstance(cfg_or_model, InterCLIP):
+            self.model = cfg_or_model
+        else:
+            cfg = cfg_or_model
+            ckpt = torch.load(cfg["CHECKPOINT"], map_location="cpu")
+            self.model = InterCLIP(cfg, device=device).load_state_dict(strip_model_prefix(ckpt["state_dict"]), strict=True)
+        if self.model.mode != "individual":
+            raise ValueError(f"EvaluatorModelWrapperIndividual: the model's MODE is {self.model.mode!r}; it needs MODE 'individual'")
+        self.cfg = self.model.cfg
+        self.device = self.model.device
+        self.extended = bool(self.cfg.get("EXTENDED", False))
+
+    @staticmethod
+    def _motion_batch(batch_data):
+        motion1, motion2, motion_lens = batch_data[2], batch_data[3], batch_data[4]
+        f = lambda m: torch.as_tensor(np.asarray(m) if not torch.is_tensor(m) else m).detach().float()
+        motion_lens = torch.as_tensor(np.asarray(motion_lens) if not torch.is_tensor(motion_lens) else motion_lens).reshape(-1).cpu()
+        return {"motions": torch.cat([f(motion1), f(motion2)], dim=-1), "motion_lens": motion_lens}
+
+    @staticmethod
+    def _text_batch(batch_data):
+        if len(batch_data) < 7 or batch_data[5] is None or batch_data[6] is None:
+            raise ValueError("EvaluatorModelWrapperIndividual.get_co_embeddings: the batch carries no text_individual1 / text_individual2 "
+                             "(name, text, motion1, motion2, motion_lens, text_individual1, text_individual2): the dataset must be built with EXTENDED: True")
+        t1, t2 = batch_data[5], batch_data[6]
+        if torch.is_tensor(t1) or isinstance(t1, np.ndarray):
+            t1, t2 = torch.as_tensor(t1), torch.as_tensor(t2)
+            return {"tokens_text": torch.stack([t1, t2], dim=1).reshape(2 * t1.shape[0], -1)}
+        t1, t2 = list(t1), list(t2)
+        return {"text": [t1[i // 2] if i % 2 == 0 else t2[i // 2] for i in range(2 * len(t1))]}          # utils.py:282
+
+    def get_co_embeddings(self, batch_data):
+        """(name, text, motion1, motion2, motion_lens, text_individual1, text_individual2) -> (text_embedding, motion_embedding), both [2B, 512] in the
+        interleaved order.  text_individual1 / 2 may be tensors of token ids [B, L] in place of the prompts."""
+        with torch.no_grad():
+            text = self._text_batch(batch_data)
+            motion_embedding = self.model.encode_motion_individual(self._motion_batch(batch_data))["motion_emb"]
+            text_embedding = self.model.encode_text(text)["text_emb"]
+        return text_embedding, motion_embedding
+
+    def get_motion_embeddings(self, batch_data):
+        with torch.no_grad():
+            return self.model.encode_motion_individual(self._motion_batch(batch_data))["motion_emb"]
 
 
 # ---- metrics (float64 numpy / scipy on the host) ---------------------------------------------------------------------------------------
@@ -316,6 +403,23 @@ def _batches(items, batch_size):
                torch.as_tensor([int(d["motion_lens"]) for d in chunk]))
 
 
+def _individual_text_of(items, k):
+    if all(f"tokens_individual{k}" in d for d in items):
+        return torch.stack([torch.as_tensor(d[f"tokens_individual{k}"]).reshape(-1) for d in items])
+    if all(f"text_individual{k}" in d for d in items):
+        return [d[f"text_individual{k}"] for d in items]
+    return None
+
+
+def _batches_individual(items, batch_size):
+    """The 7-tuples of the individual wrapper; the two individual texts are None where the items carry none (the wrapper refuses them by name)."""
+    items = list(items)
+    for i in range(0, len(items), batch_size):
+        chunk = items[i:i + batch_size]
+        yield ("generated", None, np.stack([np.asarray(d["motion1"]) for d in chunk]), np.stack([np.asarray(d["motion2"]) for d in chunk]),
+               torch.as_tensor([int(d["motion_lens"]) for d in chunk]), _individual_text_of(chunk, 1), _individual_text_of(chunk, 2))
+
+
 def evaluate_generated(wrapper, generated, mm_generated=(), groundtruth=None, batch_size=32, diversity_times=125, mm_num_times=5):
     """Scores the lists generate_for_evaluation returns, the way evaluate_matching_score / evaluate_fid / evaluate_diversity /
     evaluate_multimodality do (scripts/eval/mixermdm.py:17-114; the defaults are that script's constants).  generated / groundtruth: lists of
@@ -323,7 +427,12 @@ def evaluate_generated(wrapper, generated, mm_generated=(), groundtruth=None, ba
     ...}.  Batches of `batch_size` in list order; a last partial batch is scored too (the reference's DataLoader drops it).
     Returns {"mm_dist", "r_precision" [top 1..3], "diversity", "multimodality", and "fid" when groundtruth is given}; "diversity" is None when
     there are not more than `diversity_times` motions.  The two sampled metrics draw from np.random.  The fp32 embeddings are widened to float64
-    before any metric is formed (the reference hands its functions the fp32 arrays)."""
+    before any metric is formed (the reference hands its functions the fp32 arrays).
+    An EvaluatorModelWrapperIndividual (``wrapper.individual``) scores every person on its own: the items carry "text_individual1" / "text_individual2" (or
+    "tokens_individual1" / "tokens_individual2"), and every metric is formed over the 2B embeddings of a batch, as the reference's evaluation() does with
+    that wrapper."""
+    if getattr(wrapper, "individual", False):
+        return _evaluate_generated_individual(wrapper, generated, mm_generated, groundtruth, batch_size, diversity_times, mm_num_times)
     mm_sum, top_k, n, acts = 0.0, np.zeros(3), 0, []
     for batch in _batches(generated, batch_size):
         text_emb, motion_emb = wrapper.get_co_embeddings(batch)
@@ -349,4 +458,67 @@ def evaluate_generated(wrapper, generated, mm_generated=(), groundtruth=None, ba
         lens = torch.as_tensor([int(d["motion_lens"])] * mo.shape[0])
         mm.append(wrapper.get_motion_embeddings(("mm_generated", None, mo[:, :, 0], mo[:, :, 1], lens)).unsqueeze(0))
     out["multimodality"] = calculate_multimodality(torch.cat(mm, dim=0).double().cpu().numpy(), mm_num_times) if mm else 0
+    return out
+
+
+def _evaluate_generated_individual(wrapper, generated, mm_generated, groundtruth, batch_size, diversity_times, mm_num_times):
+    """evaluate_generated with the individual wrapper: the same metrics over the 2B per-person embeddings of every batch."""
+    mm_sum, top_k, n, acts = 0.0, np.zeros(3), 0, []
+    for batch in _batches_individual(generated, batch_size):
+        text_emb, motion_emb = wrapper.get_co_embeddings(batch)
+        t, m = text_emb.double().cpu().numpy(), motion_emb.double().cpu().numpy()
+        dist = euclidean_distance_matrix(t, m)
+        mm_sum += dist.trace()
+        top_k = top_k + calculate_top_k(np.argsort(dist, axis=1), top_k=3).sum(axis=0)
+        n += t.shape[0]
+        acts.append(m)
+    if not n:
+        raise ValueError("evaluate_generated: no generated motions")
+    acts = np.concatenate(acts, axis=0)
+    out = {"mm_dist": float(mm_sum / n), "r_precision": top_k / n}
+    if groundtruth is not None:
+        gt = np.concatenate([wrapper.get_motion_embeddings(b).double().cpu().numpy() for b in _batches_individual(groundtruth, batch_size)], axis=0)
+        gt_mu, gt_cov = calculate_activation_statistics(gt)
+        mu, cov = calculate_activation_statistics(acts)
+        out["fid"] = calculate_frechet_distance(gt_mu, gt_cov, mu, cov)
+    out["diversity"] = calculate_diversity(acts, diversity_times) if acts.shape[0] > diversity_times else None
+    mm = []
+    for d in mm_generated:
+        mo = np.asarray(d["mm_motions"])
+        lens = torch.as_tensor([int(d["motion_lens"])] * mo.shape[0])
+        mm.append(wrapper.get_motion_embeddings(("mm_generated", None, mo[:, :, 0], mo[:, :, 1], lens)).unsqueeze(0))
+    out["multimodality"] = calculate_multimodality(torch.cat(mm, dim=0).double().cpu().numpy(), mm_num_times) if mm else 0
+    return out
+
+
+# ---- replications and the F-score (scripts/eval/mixermdm.py:117-121, 216-241) ------------------------------------------------------------------
+def summarize_replications(metric_dicts):
+    """[{metric: value}, ...] of several replications -> {metric: {"mean", "conf_interval"}} with conf_interval = 1.96 * std / sqrt(n) (get_metric_statistics:
+    np.mean / np.std over the replications, element-wise for the R-precision array).  A metric that is None in any replication is left out."""
+    metric_dicts = list(metric_dicts)
+    if not metric_dicts:
+        raise ValueError("summarize_replications: no replications")
+    out = {}
+    for k in metric_dicts[0]:
+        vals = [d[k] for d in metric_dicts]
+        if any(v is None for v in vals):
+            continue
+        v = np.asarray(vals, dtype=np.float64)
+        out[k] = {"mean": np.mean(v, axis=0), "conf_interval": 1.96 * np.std(v, axis=0) / np.sqrt(v.shape[0])}
+    return out
+
+
+def f_score_summary(summary_interaction, summary_individual):
+    """The harmonic mean of interaction and individual quality (calculate_f_score): per metric of both summaries (summarize_replications' layout),
+    {"f_score": 2 a b / (a + b), "conf_interval": (ci_a + ci_b) / 2} of the means a, b and the intervals, element-wise for R-precision; where both means
+    are 0 the F-score is 0.  Metrics that only one summary holds are left out.  Returns a dictionary; writes no log file."""
+    out = {}
+    for k, si in summary_interaction.items():
+        if k not in summary_individual:
+            continue
+        a, b = np.asarray(si["mean"], dtype=np.float64), np.asarray(summary_individual[k]["mean"], dtype=np.float64)
+        ca, cb = np.asarray(si["conf_interval"], dtype=np.float64), np.asarray(summary_individual[k]["conf_interval"], dtype=np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f = np.where(a + b == 0, 0.0, 2 * a * b / (a + b))          # two zero means (an R-precision of 0 on both sides): 0, where the reference prints nan
+        out[k] = {"f_score": f if f.ndim else np.float64(f), "conf_interval": (cb + ca) / 2}
     return out

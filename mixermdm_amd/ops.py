@@ -248,6 +248,43 @@ def motion_tokens_(h, query_token, pe, seq_off, seq_len, max_len, build=0):
     return h
 
 
+def center_motion(motions, npers=2, out=None):
+    """smpl_to_ih(center_motion(ih_to_smpl(.))) of every person of every item on its own (mmdm_center_motion_f32): motions [B, Tpad, npers * 262]
+    (last-dim stride 1) -> a new tensor of that shape, all Tpad frames; channels 258..261 of every person are 0.  The floor is the minimum of position Y
+    over ALL Tpad frames of the buffer, not over an item's length (the reference centres the padded buffer); frame 0 supplies the root XZ and the facing.
+    The cross product runs along the last dimension for every B: the reference's torch.cross without dim goes wrong at a per-call batch of exactly 3,
+    which is not reproduced.  `out` must not overlap `motions`."""
+    _chk(motions, out)
+    assert motions.dim() == 3 and motions.stride(2) == 1 and motions.shape[2] == npers * 262
+    B, T, _ = motions.shape
+    if out is None:
+        out = torch.empty(B, T, npers * 262, device=motions.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape == motions.shape and out.stride(2) == 1
+    floor_ws = torch.empty(max(B * npers, 1), device=motions.device, dtype=torch.float32)
+    check(load_library().mmdm_center_motion_f32(_p(motions), motions.stride(0), motions.stride(1), T, B, int(npers), _p(out), out.stride(0), out.stride(1),
+                                                _p(floor_ws), _stream()))
+    return out
+
+
+def center_pack(motions, seq_off, seq_len, max_len, total_rows, k_pad=None, out=None):
+    """The embedding operand of the InterCLIP INDIVIDUAL evaluator in one pass (mmdm_center_pack_f32): motions [B, Tpad, 524] -> A [total_rows, k_pad], bitwise
+    motion_pack(center_motion(motions).view(2B, Tpad, 262), ..., npers=1).  Sequence 2 * i + p is person p of item i (seq_off / seq_len int32 device tensors
+    [2B]): token row and columns from 258 on zeros, frame t at row seq_off[s] + 1 + t.  Frames at and beyond a length are neither transformed nor written,
+    but their position Y enters the floor (see center_motion).  k_pad: 272 unless given.  Rows outside every sequence are left as they are in `out` (a new
+    tensor: uninitialised)."""
+    _chk(motions)
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    assert motions.dim() == 3 and motions.stride(2) == 1 and motions.shape[2] == 524 and nseq == 2 * motions.shape[0]
+    k_pad = (258 + 15) // 16 * 16 if k_pad is None else int(k_pad)
+    if out is None:
+        out = torch.empty(total_rows, k_pad, device=motions.device, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= total_rows and out.shape[1] == k_pad
+    floor_ws = torch.empty(max(nseq, 1), device=motions.device, dtype=torch.float32)
+    check(load_library().mmdm_center_pack_f32(_p(motions), motions.stride(0), motions.stride(1), motions.shape[1], motions.shape[0], _p(out), out.stride(0), k_pad,
+                                              po, pl, int(max_len), int(total_rows), _p(floor_ws), _stream()))
+    return out
+
+
 def l2_normalize(x, scale, build=0):
     """x / ||x||_2 * scale over the last dimension (mmdm_l2_normalize_rows_f32); scale: a one-element fp32 DEVICE tensor (InterCLIP's latent_scale).
     build as in `adaln`."""
