@@ -356,6 +356,8 @@ int mmdm_rowop_mdm_unpack_rag(const float* src, float* dst, int groups, int D, i
 /* out[b,l,:] = table[tokens[b,l],:] + pos[l,:]; tokens: DEVICE int32 [n,L], clamped to [0, vocab).
  * Replaces token_embedding(text) + positional_embedding  src/models/mixermdm.py:298-299. */
 int mmdm_token_embed_f32(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, void* stream);
+/* The same in either build of the row kernels (build as in mmdm_layernorm_split; 0 is mmdm_token_embed_f32): the text encoder of the evaluator's fp32_split mode takes 1. */
+int mmdm_rowop_token_embed(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, int build, void* stream);
 
 /* dst[i,:] = src[idx[i],:]; idx: DEVICE int32 [n].  Replaces out[arange(B), text.argmax(-1)] (EOT row)  src/models/mixermdm.py:311. */
 int mmdm_gather_rows_f32(const float* src, const int* idx, float* dst, int n, int D, void* stream);
@@ -387,6 +389,35 @@ int mmdm_encoder_layer_f32(float* x, const mmdm_encoder_layer_weights* w, int ns
 int mmdm_encoder_layer_ragged_f32(float* x, const mmdm_encoder_layer_weights* w, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows,
                                   int D, int H, int F, int norm_first, int activation, float eps, float* workspace, size_t workspace_floats, void* stream);
 
+/* The same post-norm layer on SPLIT operands (the fp32_split precision mode without a sampler handle: the InterCLIP evaluator): fp32 results from the fp16
+ * matrix cores.  A post-norm layer uses its input row as GEMM operand AND as residual, so the caller hands both: x fp32 [R, D] (in place) and xs, the rows' two
+ * fp16 planes [2][R][D] (mmdm_f32_split of x; xs_plane_stride in elements, a multiple of 8, >= R * D).  The caller provides xs for the FIRST layer (the
+ * sequence assembly writes it: mmdm_rowop_motion_tokens_split, mmdm_rowop_mdm_pack); the layer rewrites both for the next one; last != 0 skips the final plane
+ * write (nothing reads the planes of the last layer's output; xs then holds the planes of LN1's output).
+ *   Q|K|V = planes(xs W_in^T + b) -> two-plane attention with MMDM_ATTN_NO_ZERO_KEY -> planes;  x, xs = LN1(att W_out^T + b + x);
+ *   x, xs = LN2(planes(gelu(xs W_1^T + b)) W_2^T + b + x)                       (every GEMM is mmdm_linear_split, the LayerNorm mmdm_layernorm_split)
+ * Weights: the four GEMM matrices as fp16 planes [2][N][K] with plane stride N * K (mmdm_f32_split of the fp32 matrix), or -- packed != 0 -- the same in
+ * fragment order (mmdm_split_pack_weight; needs D % 64 == 0 and F % 64 == 0); biases and norms fp32.  Activation: GELU (erf).
+ * Head sizes 64 and 128 run the two-plane attention.  Any other head size <= 256 (the evaluator's text stack: 768 / 8 = 96) runs the fp32 attention, as a
+ * precision-2 sampler stack at such a head size does: the QKV GEMM then writes fp32 rows and the attention splits its output on the way out.
+ * The ragged form (sequences as in mmdm_encoder_layer_ragged_f32) covers head sizes 64 and 128 only; every sequence's rows are BITWISE those of the uniform
+ * form on that sequence alone, rows outside every sequence are unspecified afterwards and influence nothing.
+ * Every row kernel comes from the build without packed-fp32 instructions (build 1 of mmdm_layernorm_split): the layer launches what a precision-2 handle launches.
+ * MMDM_ERR_UNSUPPORTED, by name: norm_first != 0, D % 32 != 0, F % 32 != 0, a head size the form does not cover.  RANGE: |value| < 65504 in every operand (as
+ * precision 2 of mmdm_config).  workspace: mmdm_encoder_layer_split_workspace(nseq, T, D, F) floats, 16-byte aligned (ragged: nseq = 1, T = total_rows). */
+typedef struct {
+    const void *in_proj_planes, *out_proj_planes, *linear1_planes, *linear2_planes;   /* fp16 [2][3D][D], [2][D][D], [2][F][D], [2][D][F] */
+    const float *in_proj_bias, *out_proj_bias, *linear1_bias, *linear2_bias;          /* [3D], [D], [F], [D] */
+    const float *norm1_weight, *norm1_bias, *norm2_weight, *norm2_bias;               /* [D] each */
+    int packed;                                                                       /* != 0: the four matrices are in fragment order */
+} mmdm_encoder_layer_split_weights;
+size_t mmdm_encoder_layer_split_workspace(int nseq, int T, int D, int F);
+int mmdm_encoder_layer_split(float* x, void* xs, int64_t xs_plane_stride, const mmdm_encoder_layer_split_weights* w, int nseq, int T, int D, int H, int F,
+                             int norm_first, float eps, int last, float* workspace, size_t workspace_floats, void* stream);
+int mmdm_encoder_layer_ragged_split(float* x, void* xs, int64_t xs_plane_stride, const mmdm_encoder_layer_split_weights* w, int nseq, const int* seq_off,
+                                    const int* seq_len, int max_len, int total_rows, int D, int H, int F, int norm_first, float eps, int last, float* workspace,
+                                    size_t workspace_floats, void* stream);
+
 /* The InterCLIP evaluator's row kernels (src/evaluation/models.py:57-74, 152, 178), in either build of the row kernels (build as in mmdm_layernorm_split).
  * Item s of a batch is a TOKEN SEQUENCE of seq_len[s] rows -- the query token, then its first seq_len[s] - 1 frames -- at rows [seq_off[s], seq_off[s] +
  * seq_len[s]) of a packed row space of total_rows rows (seq_off / seq_len: DEVICE ints [nseq], nseq <= 65535; max_len >= every length sizes the grid).
@@ -398,11 +429,22 @@ int mmdm_encoder_layer_ragged_f32(float* x, const mmdm_encoder_layer_weights* w,
  *   l2_normalize:   out[r] = x[r] / ||x[r]||_2 * scale[0] for x [rows, D] (scale: a DEVICE pointer -- the latent_scale parameter; D % 4 == 0, D <= 2048; in
  *                   place allowed).  fp32 throughout; the sum of squares is reduced in a fixed order, so a row's bits do not depend on `rows`.
  *                   mmdm_l2_normalize_rows_f32 is build 0.
- * Rows outside every sequence are not written. */
+ * Rows outside every sequence are not written.
+ * The plane-writing forms (the evaluator in the fp32_split mode; both builds):
+ *   motion_pack_split:    the same operand written directly as the two fp16 planes of mmdm_linear_split's A, planes [2][total_rows][lda] (plane_stride in
+ *                         elements, >= total_rows * lda) -- BITWISE mmdm_f32_split of motion_pack's A.  Kp must be a multiple of 32 for that GEMM (544 for two
+ *                         persons, 288 for one); pad columns and token rows are +0 in both planes.
+ *   motion_tokens_split:  motion_tokens that also writes the rows' two fp16 planes [2][total_rows][D] in the same pass (layer 0's operand: the role
+ *                         mmdm_rowop_mdm_pack's planes play for MDM); h is bitwise motion_tokens', the planes mmdm_f32_split of it.  planes 8-byte aligned,
+ *                         plane_stride % 4 == 0. */
 int mmdm_rowop_motion_pack(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, int lda, int Kp, int nseq,
                            const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream);
 int mmdm_rowop_motion_tokens(float* h, const float* query_token, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len,
                              int max_len, int total_rows, int build, void* stream);
+int mmdm_rowop_motion_pack_split(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, void* planes, int lda, int64_t plane_stride, int Kp,
+                                 int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream);
+int mmdm_rowop_motion_tokens_split(float* h, void* planes, int64_t plane_stride, const float* query_token, const float* pe, int pe_rows, int D, int nseq,
+                                   const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream);
 int mmdm_l2_normalize_rows_f32(const float* x, const float* scale, float* out, int rows, int D, void* stream);
 int mmdm_rowop_l2_normalize(const float* x, const float* scale, float* out, int rows, int D, int build, void* stream);
 
@@ -420,11 +462,16 @@ int mmdm_rowop_l2_normalize(const float* x, const float* scale, float* out, int 
  * (joints 2, 1); the facing rotation is qbetween(normalize(cross(Y, across)), +Z), the cross product along the last dimension for every batch size (the
  * reference's torch.cross without dim goes wrong at a per-call batch of exactly 3: not reproduced).  A NaN position Y is dropped by the minimum where
  * torch.min would propagate it, and coincident hips divide by zero as in the reference: neither is pinned.
+ *   center_pack_split: center_pack written directly as the two fp16 planes of mmdm_linear_split's A, planes [2][total_rows][lda] (plane_stride in elements,
+ *                  >= total_rows * lda): BITWISE mmdm_f32_split of center_pack's A (every value is formed as there and split on its way out).
  * floor_ws: [nitems * npers] floats of the caller's (center_pack: [nitems * 2]); nothing is allocated inside the call. */
 int mmdm_center_motion_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, int npers, float* out, int64_t out_item_stride,
                            int out_row_stride, float* floor_ws, void* stream);
 int mmdm_center_pack_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, float* A, int lda, int Kp, const int* seq_off,
                          const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream);
+
+int mmdm_center_pack_split(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, void* planes, int lda, int64_t plane_stride, int Kp,
+                           const int* seq_off, const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 2. The sampler handle: weights + workspace + captured step graph.

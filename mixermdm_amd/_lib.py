@@ -42,6 +42,12 @@ class EncoderLayerWeights(C.Structure):
                                            "linear2_weight", "linear2_bias", "norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")]
 
 
+class EncoderLayerSplitWeights(C.Structure):
+    """mmdm_encoder_layer_split_weights (include/mmdm.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("in_proj_planes", "out_proj_planes", "linear1_planes", "linear2_planes", "in_proj_bias", "out_proj_bias",
+                                           "linear1_bias", "linear2_bias", "norm1_weight", "norm1_bias", "norm2_weight", "norm2_bias")] + [("packed", C.c_int)]
+
+
 class BeginOptions(C.Structure):
     """mmdm_begin_options (include/mmdm.h)."""
     _fields_ = [("noise_source", C.c_int), ("noise_steps", C.c_int), ("noise", C.c_void_p), ("seed", C.c_ulonglong), ("x_start", C.c_void_p),
@@ -91,10 +97,18 @@ SYMBOLS = {
     "mmdm_dual_ddim_f32": (_I, [_VP, _VP, _VP, _I, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _I, _I, _I, _VP]),
     "mmdm_layernorm_f32": (_I, [_VP, _VP, _VP, _VP, _I, _I, C.c_float, _VP]),
     "mmdm_token_embed_f32": (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "mmdm_rowop_token_embed": (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "mmdm_gather_rows_f32": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "mmdm_encoder_layer_workspace": (C.c_size_t, [_I, _I, _I, _I]),
     "mmdm_encoder_layer_f32": (_I, [_VP, C.POINTER(EncoderLayerWeights), _I, _I, _I, _I, _I, _I, _I, _I, C.c_float, _VP, C.c_size_t, _VP]),
     "mmdm_encoder_layer_ragged_f32": (_I, [_VP, C.POINTER(EncoderLayerWeights), _I, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, C.c_float, _VP, C.c_size_t, _VP]),
+    "mmdm_encoder_layer_split_workspace": (C.c_size_t, [_I, _I, _I, _I]),
+    "mmdm_encoder_layer_split": (_I, [_VP, _VP, C.c_int64, C.POINTER(EncoderLayerSplitWeights), _I, _I, _I, _I, _I, _I, C.c_float, _I, _VP, C.c_size_t, _VP]),
+    "mmdm_encoder_layer_ragged_split": (_I, [_VP, _VP, C.c_int64, C.POINTER(EncoderLayerSplitWeights), _I, _VP, _VP, _I, _I, _I, _I, _I, _I, C.c_float, _I, _VP,
+                                             C.c_size_t, _VP]),
+    "mmdm_rowop_motion_pack_split": (_I, [_VP, C.c_int64, _I, _I, _I, _VP, _I, C.c_int64, _I, _I, _VP, _VP, _I, _I, _I, _VP]),
+    "mmdm_rowop_motion_tokens_split": (_I, [_VP, _VP, C.c_int64, _VP, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP]),
+    "mmdm_center_pack_split": (_I, [_VP, C.c_int64, _I, _I, _I, _VP, _I, C.c_int64, _I, _VP, _VP, _I, _I, _VP, _VP]),
     "mmdm_rowop_motion_pack": (_I, [_VP, C.c_int64, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP]),
     "mmdm_rowop_motion_tokens": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP]),
     "mmdm_l2_normalize_rows_f32": (_I, [_VP, _VP, _VP, _I, _I, _VP]),

@@ -537,29 +537,44 @@ __global__ __launch_bounds__(256) void center_motion_kernel(const float* __restr
 // seq_len[s] - 1 frames, 258 centred channels each, columns [258, Kp) zeros.  32 threads per row, 8 rows per block: lanes 0..21 are the joints, the other
 // ten write the zero columns.  Frames at and beyond the length are never transformed or written (only their position Y is read, by the floor); rows
 // outside every sequence are not touched.
+// SPLIT: the same elements as the two fp16 planes of the fp32-split embedding GEMM's A operand ([2][total_rows][lda], plane stride in elements) instead of
+// fp32 rows -- each value is formed exactly as in the fp32 form and split on its way out (kernels.h mmdm_split2), a zero is +0 in both planes.
+template <bool SPLIT>
+__device__ __forceinline__ void pack_store(void* __restrict__ A, size_t plane, size_t i, float v) {
+    if constexpr (SPLIT) {
+        _Float16 hi, lo;
+        mmdm_split2(v, hi, lo);
+        static_cast<_Float16*>(A)[i] = hi;
+        static_cast<_Float16*>(A)[plane + i] = lo;
+    } else {
+        static_cast<float*>(A)[i] = v;
+    }
+}
+
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void center_pack_kernel(const float* __restrict__ m, long long item_stride, int row_stride, int Tpad,
-                                                           float* __restrict__ A, int lda, int Kp, const int* __restrict__ seq_off,
+                                                           void* __restrict__ A, size_t plane, int lda, int Kp, const int* __restrict__ seq_off,
                                                            const int* __restrict__ seq_len, int total_rows, const float* __restrict__ floor_ws) {
     const int s = blockIdx.y, pos = blockIdx.x * 8 + (threadIdx.x >> 5), l = threadIdx.x & 31;
     if (pos >= seq_len[s] || pos > Tpad) return;
     const long long row = (long long)seq_off[s] + pos;
     if (row < 0 || row >= total_rows) return;
-    float* ap = A + (size_t)row * lda;
+    const size_t r0 = (size_t)row * lda;
     if (pos == 0) {
-        for (int c = l; c < Kp; c += 32) ap[c] = 0.f;
+        for (int c = l; c < Kp; c += 32) pack_store<SPLIT>(A, plane, r0 + c, 0.f);
         return;
     }
     if (l >= NJ) {
-        for (int c = FEET0 + (l - NJ); c < Kp; c += 32 - NJ) ap[c] = 0.f;
+        for (int c = FEET0 + (l - NJ); c < Kp; c += 32 - NJ) pack_store<SPLIT>(A, plane, r0 + c, 0.f);
         return;
     }
     const float* pb = m + (size_t)(s >> 1) * item_stride + (size_t)(s & 1) * NF;
     const Centred c = center_joint(floor_ws[s], pb, pb + (size_t)(pos - 1) * row_stride, l);
-    ap[3 * l] = c.pos.x; ap[3 * l + 1] = c.pos.y; ap[3 * l + 2] = c.pos.z;
-    ap[66 + 3 * l] = c.vel.x; ap[66 + 3 * l + 1] = c.vel.y; ap[66 + 3 * l + 2] = c.vel.z;
+    pack_store<SPLIT>(A, plane, r0 + 3 * l, c.pos.x); pack_store<SPLIT>(A, plane, r0 + 3 * l + 1, c.pos.y); pack_store<SPLIT>(A, plane, r0 + 3 * l + 2, c.pos.z);
+    pack_store<SPLIT>(A, plane, r0 + 66 + 3 * l, c.vel.x); pack_store<SPLIT>(A, plane, r0 + 66 + 3 * l + 1, c.vel.y); pack_store<SPLIT>(A, plane, r0 + 66 + 3 * l + 2, c.vel.z);
     if (l < 21) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) ap[ROT0 + 6 * l + k] = c.rot[k];
+        for (int k = 0; k < 6; ++k) pack_store<SPLIT>(A, plane, r0 + ROT0 + 6 * l + k, c.rot[k]);
     }
 }
 
@@ -908,22 +923,40 @@ extern "C" int mmdm_center_motion_f32(const float* motions, int64_t item_stride,
     return mmdm_check_launch("center_motion");
 }
 
-extern "C" int mmdm_center_pack_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, float* A, int lda, int Kp,
-                                    const int* seq_off, const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream) {
+// planes != null: the operand as two fp16 planes (mmdm_center_pack_split) instead of the fp32 rows A; exactly one is given
+static int center_pack(const char* who, const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, float* A, void* planes, int64_t plane_stride,
+                       int lda, int Kp, const int* seq_off, const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream) {
     if (nitems == 0) return MMDM_OK;
-    if (int rc = center_args_check("mmdm_center_pack_f32", motions, item_stride, row_stride, Tpad, nitems, 2, floor_ws)) return rc;
+    if (int rc = center_args_check(who, motions, item_stride, row_stride, Tpad, nitems, 2, floor_ws)) return rc;
     // the sequence description of mmdm_rowop_motion_pack, two sequences per item
     if (!seq_off || !seq_len || 2 * (int64_t)nitems > 65535 || max_len <= 0 || total_rows <= 0)
-        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_pack_f32: bad sequence description nseq=%lld (<= 65535) max_len=%d total_rows=%d", 2 * (long long)nitems, max_len,
-                              total_rows);
-    if (!A || Kp < MMDM_NF - 4 || lda < Kp) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_pack_f32: bad operand Kp=%d lda=%d", Kp, lda);
-    if (max_len - 1 > Tpad) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_center_pack_f32: max_len=%d sequences need %d frames, the buffer holds %d", max_len, max_len - 1, Tpad);
+        return mmdm_set_error(MMDM_ERR_ARG, "%s: bad sequence description nseq=%lld (<= 65535) max_len=%d total_rows=%d", who, 2 * (long long)nitems, max_len, total_rows);
+    if ((!A && !planes) || Kp < MMDM_NF - 4 || lda < Kp) return mmdm_set_error(MMDM_ERR_ARG, "%s: bad operand Kp=%d lda=%d", who, Kp, lda);
+    if (planes && plane_stride < (int64_t)total_rows * lda)
+        return mmdm_set_error(MMDM_ERR_ARG, "%s: plane stride %lld < total_rows * lda = %lld", who, (long long)plane_stride, (long long)total_rows * lda);
+    if (max_len - 1 > Tpad) return mmdm_set_error(MMDM_ERR_ARG, "%s: max_len=%d sequences need %d frames, the buffer holds %d", who, max_len, max_len - 1, Tpad);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(center_floor_kernel, dim3(nitems * 2), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, 2, floor_ws);
     if (int rc = mmdm_check_launch("center_floor")) return rc;
-    hipLaunchKernelGGL(center_pack_kernel, dim3((max_len + 7) / 8, nitems * 2), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, A, lda, Kp, seq_off,
-                       seq_len, total_rows, floor_ws);
+    const dim3 grid((max_len + 7) / 8, nitems * 2), block(256);
+    if (planes)
+        hipLaunchKernelGGL(center_pack_kernel<true>, grid, block, 0, st, motions, (long long)item_stride, row_stride, Tpad, planes, (size_t)plane_stride, lda, Kp, seq_off,
+                           seq_len, total_rows, floor_ws);
+    else
+        hipLaunchKernelGGL(center_pack_kernel<false>, grid, block, 0, st, motions, (long long)item_stride, row_stride, Tpad, static_cast<void*>(A), (size_t)0, lda, Kp, seq_off,
+                           seq_len, total_rows, floor_ws);
     return mmdm_check_launch("center_pack");
+}
+
+extern "C" int mmdm_center_pack_f32(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, float* A, int lda, int Kp,
+                                    const int* seq_off, const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream) {
+    return center_pack("mmdm_center_pack_f32", motions, item_stride, row_stride, Tpad, nitems, A, nullptr, 0, lda, Kp, seq_off, seq_len, max_len, total_rows, floor_ws, stream);
+}
+
+extern "C" int mmdm_center_pack_split(const float* motions, int64_t item_stride, int row_stride, int Tpad, int nitems, void* planes, int lda, int64_t plane_stride, int Kp,
+                                      const int* seq_off, const int* seq_len, int max_len, int total_rows, float* floor_ws, void* stream) {
+    return center_pack("mmdm_center_pack_split", motions, item_stride, row_stride, Tpad, nitems, nullptr, planes, plane_stride, lda, Kp, seq_off, seq_len, max_len,
+                       total_rows, floor_ws, stream);
 }
 
 int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rows& r, hipStream_t st) {

@@ -162,8 +162,8 @@ int mmdm_linear_fp8_ex(const void* A, int lda, const float* a_scale, const void*
                        int out_mode, int M, int N, int K, int epilogue, const float* extra, int ld_extra, int period, void* bf16_copy, int ld2, int copy_cols,
                        float a_const, float out_scale, void* stream);
 // The row operations a handle's step uses (rowops.hip), one table per build of that file: mmdm_rowops_tab is rowops.o as it stands (precision 0 handles and
-// the stateless entry points), mmdm_rowops_tab_nopk is rowops_nopk.o -- the same kernels without packed-fp32 VALU instructions (mixermdm_amd/build.py),
-// which precision 1-3 handles take.  A caller picks the table once (mmdm.hip Ctx::ro) and calls through it.
+// the stateless fp32 entry points), mmdm_rowops_tab_nopk is rowops_nopk.o -- the same kernels without packed-fp32 VALU instructions (mixermdm_amd/build.py),
+// which precision 1-3 handles and the stateless SPLIT encoder layer (mmdm_encoder_layer_split: it launches the packed-W GEMMs itself) take.  A caller picks the table once (mmdm.hip Ctx::ro) and calls through it.
 struct mmdm_rowops {
     // row_seq != nullptr: ragged batch -- `rows_rag` rows in all, row r belongs to sequence row_seq[r] (device array); nseq / T are then unused
     int (*adaln)(const float* h, const float* ss, int ss_ld, int ss_rows, void* out, int out_mode, float* row_scale, int nseq, int T, int D, void* stream,
@@ -186,12 +186,16 @@ struct mmdm_rowops {
     // query token, then seq_len[s] - 1 frames; device arrays, max_len sizes the grid).  motion_pack: the embedding GEMM's A operand [total_rows, lda] from
     // motions [nseq, Tpad, npers * 262] -- the last 4 features of every person dropped, columns [npers * 258, Kp) and the token rows zeros.
     // motion_tokens: in place on the GEMM's output h [total_rows, D] -- token row = query + pe[0], frame row 1 + t += pe[1 + t].
-    int (*motion_pack)(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, int lda, int Kp, int nseq, const int* seq_off,
-                       const int* seq_len, int max_len, int total_rows, hipStream_t st);
-    int (*motion_tokens)(float* h, const float* query, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len, int max_len,
-                         int total_rows, hipStream_t st);
+    // The fp32-split evaluator: motion_pack writes `planes` INSTEAD of A (exactly one is given) -- the operand as two fp16 planes [2][total_rows][lda] --
+    // and motion_tokens writes the rows' planes [2][total_rows][D] as a second output (planes != null); plane strides in elements.
+    int (*motion_pack)(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, void* planes, int64_t plane_stride, int lda, int Kp,
+                       int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, hipStream_t st);
+    int (*motion_tokens)(float* h, void* planes, int64_t plane_stride, const float* query, const float* pe, int pe_rows, int D, int nseq, const int* seq_off,
+                         const int* seq_len, int max_len, int total_rows, hipStream_t st);
     // out[r] = x[r] / ||x[r]||_2 * scale[0] (scale: device pointer)
     int (*l2_normalize)(const float* x, const float* scale, float* out, int rows, int D, hipStream_t st);
+    // out[b, l] = table[tokens[b, l]] + pos[l] (the evaluator's text encoder: in the fp32-split mode its first kernel follows the build rule too)
+    int (*token_embed)(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, hipStream_t st);
 };
 extern const mmdm_rowops mmdm_rowops_tab, mmdm_rowops_tab_nopk;
 // Sequences of a RAGGED batch as the attention kernels see them (device arrays: one captured graph serves every batch of the same row bucket):

@@ -546,11 +546,12 @@ struct Ctx {
     const unsigned char* kmask = nullptr;
     const int* klast = nullptr;
     int kmask_rows = 0;
-    // the row operations of this context, chosen once: precision 0 handles and the stateless composites take rowops.o, every other handle the build without
-    // packed-fp32 instructions (the comment above g_serialize_handles has the reason)
+    // the row operations of this context, chosen once: precision 0 handles and the stateless fp32 composites take rowops.o, every other handle the build without
+    // packed-fp32 instructions (the comment above g_serialize_handles has the reason) -- and so do the stateless SPLIT composites (nopk: they launch the
+    // packed-W GEMMs themselves, so their row kernels follow the rule of a precision-2 handle)
     const mmdm_rowops& ro;
-    Ctx(mmdm_handle h_, hipStream_t st_, const Scratch* s_, const Geom* g_ = nullptr)
-        : h(h_), st(st_), s(s_), g(g_), ro(h_ && h_->cfg.precision != 0 ? mmdm_rowops_tab_nopk : mmdm_rowops_tab) {}
+    Ctx(mmdm_handle h_, hipStream_t st_, const Scratch* s_, const Geom* g_ = nullptr, bool nopk = false)
+        : h(h_), st(st_), s(s_), g(g_), ro(nopk || (h_ && h_->cfg.precision != 0) ? mmdm_rowops_tab_nopk : mmdm_rowops_tab) {}
     Ctx on(hipStream_t st2, const Scratch* s2) const { Ctx c = *this; c.st = st2; c.s = s2; return c; }      // the same call on another stream and scratch set
     bool rag() const { return g && g->rag; }
     size_t rows_of(int nseq, int T) const { return g ? g->rows_of(nseq) : (size_t)nseq * T; }
@@ -881,25 +882,31 @@ int encoder_layer(const Ctx& c, float* x, const EncLayerW& w, int nseq, int T, i
 //   Q|K|V = planes(xs W_in^T + b)          -> the two-plane attention (plain softmax over the T keys) -> att planes
 //   tmp   = att W_out^T + b + x            (fp32)       x, xs = LN1(tmp)
 //   f1    = planes(gelu(xs W_1^T + b))                  tmp = f1 W_2^T + b + x;  x, xs = LN2(tmp)   (last layer: x only -- nothing reads its planes)
-// Weights: the layer's fp16-plane twins (EncLayerW::*_s), in fragment order when `packed`.  rg as in encoder_layer.
+// Weights: the layer's fp16-plane twins (EncLayerW::*_s), in fragment order when `packed`.  rg as in encoder_layer.  xs_plane: plane stride of xs in elements
+// (0 = R * D).  A head size other than 64 / 128 (the stateless entry points only: MDM in a handle needs 64 / 128) takes the operand form a precision-2 stack
+// takes there (Form::F32): the QKV GEMM writes fp32 rows, the fp32 attention reads them and writes its output as planes.
 int encoder_layer_split(const Ctx& c, float* x, void* xs, const EncLayerW& w, bool packed, int nseq, int T, int D, int H, int F, float eps, void* qkv, void* att,
-                        float* tmp, void* f1, bool last, const mmdm_rag_seq* rg = nullptr) {
+                        float* tmp, void* f1, bool last, const mmdm_rag_seq* rg = nullptr, size_t xs_plane = 0) {
     const int R = rg ? rg->total_rows : nseq * T, dh = D / H;
-    const size_t RD = (size_t)R * D;
-    RC(linear_s(c, xs, D, RD, w.in_s, packed ? 0 : D, (size_t)3 * D * D, w.in_b, qkv, 3 * D, (size_t)R * 3 * D, 1, R, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0));
-    {
+    const size_t RD = (size_t)R * D, XP = xs_plane ? xs_plane : RD;
+    const bool planes_attn = dh == 64 || dh == 128;
+    RC(linear_s(c, xs, D, XP, w.in_s, packed ? 0 : D, (size_t)3 * D * D, w.in_b, qkv, 3 * D, (size_t)R * 3 * D, planes_attn ? 1 : 0, R, 3 * D, D, MMDM_EPI_BIAS, nullptr, 0));
+    RC(prof_begin_plain_attn(c, nseq, T, H, dh, rg != nullptr));
+    if (planes_attn) {
         const uint16_t* q = static_cast<const uint16_t*>(qkv);
-        RC(prof_begin_plain_attn(c, nseq, T, H, dh, rg != nullptr));
         RC(mmdm_attention_planes_ex(q, 3 * D, (int64_t)R * 3 * D, q + D, 3 * D, (int64_t)R * 3 * D, 2, nullptr, 0, q + 2 * D, 3 * D, (int64_t)R * 3 * D, att, D, 2,
                                     MMDM_ATTN_NO_ZERO_KEY, nseq, T, T, H, dh, 0, c.st, rg));
-        RC(prof_end(c, 1));
+    } else {
+        const float* q = static_cast<const float*>(qkv);
+        RC(mmdm_attention_opts_rag(q, 3 * D, q + D, 3 * D, q + 2 * D, 3 * D, att, D, 2, MMDM_ATTN_NO_ZERO_KEY, nseq, T, T, H, dh, 0, rg, c.st));
     }
+    RC(prof_end(c, 1));
     RC(linear_s(c, att, D, RD, w.out_s, packed ? 0 : D, (size_t)D * D, w.out_b, tmp, D, 0, 0, R, D, D, MMDM_EPI_BIAS_RESID, x, D));
-    RC(c.ro.layernorm_planes(tmp, w.n1_g, w.n1_b, x, xs, (int64_t)RD, R, D, eps, c.st));
-    RC(linear_s(c, xs, D, RD, w.l1_s, packed ? 0 : D, (size_t)F * D, w.l1_b, f1, F, (size_t)R * F, 1, R, F, D, MMDM_EPI_BIAS_GELU, nullptr, 0));
+    RC(c.ro.layernorm_planes(tmp, w.n1_g, w.n1_b, x, xs, (int64_t)XP, R, D, eps, c.st));
+    RC(linear_s(c, xs, D, XP, w.l1_s, packed ? 0 : D, (size_t)F * D, w.l1_b, f1, F, (size_t)R * F, 1, R, F, D, MMDM_EPI_BIAS_GELU, nullptr, 0));
     RC(linear_s(c, f1, F, (size_t)R * F, w.l2_s, packed ? 0 : F, (size_t)D * F, w.l2_b, tmp, D, 0, 0, R, D, F, MMDM_EPI_BIAS_RESID, x, D));
     if (last) return c.ro.layernorm(tmp, w.n2_g, w.n2_b, x, R, D, eps, c.st);
-    return c.ro.layernorm_planes(tmp, w.n2_g, w.n2_b, x, xs, (int64_t)RD, R, D, eps, c.st);
+    return c.ro.layernorm_planes(tmp, w.n2_g, w.n2_b, x, xs, (int64_t)XP, R, D, eps, c.st);
 }
 
 // MDMDenoiser.forward (mdm.py:273-298) on the CFG-doubled batch: `cond` rows are [n, ldc] with person p's latent-sized slice at
@@ -2164,6 +2171,73 @@ extern "C" int mmdm_encoder_layer_ragged_f32(float* x, const mmdm_encoder_layer_
     Ctx c{nullptr, static_cast<hipStream_t>(stream), nullptr};
     const mmdm_rag_seq rg{seq_off, seq_len, total_rows, max_len};
     return encoder_layer(c, x, e, nseq, max_len, D, H, F, false, activation, false, eps, qkv, att, tmp, f1, &rg);
+}
+
+// ---- the post-norm layer on split operands without a handle (the InterCLIP evaluator in the fp32_split mode): the stateless faces of encoder_layer_split ----
+extern "C" size_t mmdm_encoder_layer_split_workspace(int nseq, int T, int D, int F) {
+    // Q|K|V planes (or fp32 rows) [R, 3D] | attention planes [2][R][D] | sub-layer output fp32 [R, D] | GELU planes [2][R][F]: the fp32 layer's count
+    return mmdm_encoder_layer_workspace(nseq, T, D, F);
+}
+
+static int enc_layer_split_weights(const mmdm_encoder_layer_split_weights* w, EncLayerW& e, const char* who) {
+    for (const void* q : {w->in_proj_planes, w->out_proj_planes, w->linear1_planes, w->linear2_planes})
+        if (!q) return mmdm_set_error(MMDM_ERR_ARG, "%s: null weight planes", who);
+    for (const float* q : {w->in_proj_bias, w->out_proj_bias, w->linear1_bias, w->linear2_bias, w->norm1_weight, w->norm1_bias, w->norm2_weight, w->norm2_bias})
+        if (!q) return mmdm_set_error(MMDM_ERR_ARG, "%s: null weight pointer", who);
+    auto nc = [](const float* q) { return const_cast<float*>(q); };
+    auto nv = [](const void* q) { return const_cast<void*>(q); };
+    e = EncLayerW{};
+    e.in_s = nv(w->in_proj_planes); e.out_s = nv(w->out_proj_planes); e.l1_s = nv(w->linear1_planes); e.l2_s = nv(w->linear2_planes);
+    e.in_b = nc(w->in_proj_bias); e.out_b = nc(w->out_proj_bias); e.l1_b = nc(w->linear1_bias); e.l2_b = nc(w->linear2_bias);
+    e.n1_g = nc(w->norm1_weight); e.n1_b = nc(w->norm1_bias); e.n2_g = nc(w->norm2_weight); e.n2_b = nc(w->norm2_bias);
+    return MMDM_OK;
+}
+
+// checks shared by the two entry points (R rows in all), then the layer; rg == nullptr: uniform
+static int enc_layer_split_run(const char* who, float* x, void* xs, int64_t xs_plane, const mmdm_encoder_layer_split_weights* w, int nseq, int T, size_t R, int D, int H, int F,
+                               int norm_first, float eps, int last, float* workspace, size_t workspace_floats, const mmdm_rag_seq* rg, void* stream) {
+    if (norm_first) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: norm_first is not supported (the post-norm form only)", who);
+    if (D % 32) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: D %% 32 != 0 is not supported (D=%d: the split GEMMs need K %% 32 == 0)", who, D);
+    if (F % 32) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: F %% 32 != 0 is not supported (F=%d: the split GEMMs need K %% 32 == 0)", who, F);
+    const int dh = D / H;
+    if (rg && dh != 64 && dh != 128) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: head size %d is not supported on ragged batches (64 or 128)", who, dh);
+    if (dh > 256) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: head size %d is not supported (<= 256)", who, dh);
+    if (w->packed && ((D & 63) || (F & 63)))
+        return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: weights in fragment order need D %% 64 == 0 and F %% 64 == 0 (D=%d F=%d)", who, D, F);
+    if (xs_plane < (int64_t)(R * D) || (xs_plane & 7)) return mmdm_set_error(MMDM_ERR_ARG, "%s: plane stride %lld must be a multiple of 8 and >= rows * D", who, (long long)xs_plane);
+    if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(workspace)) & 15))
+        return mmdm_set_error(MMDM_ERR_ARG, "%s: x, xs and the workspace must be 16-byte aligned", who);
+    const size_t need = R * ((size_t)5 * D + F);
+    if (workspace_floats < need) return mmdm_set_error(MMDM_ERR_ARG, "%s: workspace too small (%zu < %zu floats)", who, workspace_floats, need);
+    EncLayerW e;
+    RC(enc_layer_split_weights(w, e, who));
+    RC(mmdm_kernels_init());
+    float* qkv = workspace;
+    float* att = qkv + R * 3 * D;
+    float* tmp = att + R * D;
+    float* f1 = tmp + R * D;
+    Ctx c{nullptr, static_cast<hipStream_t>(stream), nullptr, nullptr, true};
+    return encoder_layer_split(c, x, xs, e, w->packed != 0, nseq, T, D, H, F, eps, qkv, att, tmp, f1, last != 0, rg, (size_t)xs_plane);
+}
+
+extern "C" int mmdm_encoder_layer_split(float* x, void* xs, int64_t xs_plane_stride, const mmdm_encoder_layer_split_weights* w, int nseq, int T, int D, int H, int F,
+                                        int norm_first, float eps, int last, float* workspace, size_t workspace_floats, void* stream) {
+    if (nseq == 0 || T == 0) return MMDM_OK;
+    if (!x || !xs || !w || !workspace || nseq < 0 || T < 0 || D <= 0 || H <= 0 || D % H || F <= 0 || (int64_t)nseq * T > 0x7fffffff)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_split: bad arguments nseq=%d T=%d D=%d H=%d F=%d", nseq, T, D, H, F);
+    return enc_layer_split_run("mmdm_encoder_layer_split", x, xs, xs_plane_stride, w, nseq, T, (size_t)nseq * T, D, H, F, norm_first, eps, last, workspace, workspace_floats,
+                               nullptr, stream);
+}
+
+extern "C" int mmdm_encoder_layer_ragged_split(float* x, void* xs, int64_t xs_plane_stride, const mmdm_encoder_layer_split_weights* w, int nseq, const int* seq_off,
+                                               const int* seq_len, int max_len, int total_rows, int D, int H, int F, int norm_first, float eps, int last, float* workspace,
+                                               size_t workspace_floats, void* stream) {
+    if (nseq == 0 || total_rows == 0) return MMDM_OK;
+    if (!x || !xs || !w || !workspace || !seq_off || !seq_len || nseq < 0 || max_len <= 0 || total_rows < 0 || D <= 0 || H <= 0 || D % H || F <= 0)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_encoder_layer_ragged_split: bad arguments nseq=%d max_len=%d total_rows=%d D=%d H=%d F=%d", nseq, max_len, total_rows, D, H, F);
+    const mmdm_rag_seq rg{seq_off, seq_len, total_rows, max_len};
+    return enc_layer_split_run("mmdm_encoder_layer_ragged_split", x, xs, xs_plane_stride, w, nseq, max_len, (size_t)total_rows, D, H, F, norm_first, eps, last, workspace,
+                               workspace_floats, &rg, stream);
 }
 
 extern "C" int mmdm_profile_enable(mmdm_handle h, int on) {

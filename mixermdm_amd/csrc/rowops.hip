@@ -462,14 +462,14 @@ __global__ void gauss1d_kernel(const float* __restrict__ x, float* __restrict__ 
 // A[row, q * 258 + j] = motions[s, p - 1, q * 262 + j] for j < 258 (x.reshape(B, T, 2, -1)[..., :-4]); columns [npers * 258, Kp) and the token row are zeros.
 // Frames at and beyond seq_len[s] - 1 are never read.  A plain 4-byte loop: person 1 starts 1048 bytes into a motion row and 1032 bytes into an A row, so the
 // two sides share no 16-byte phase; consecutive lanes still read and write consecutive words.
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void motion_pack_kernel(const float* __restrict__ motions, long long item_stride, int row_stride, int Tpad, int npers,
-                                                           float* __restrict__ A, int lda, int Kp, const int* __restrict__ seq_off,
+                                                           void* __restrict__ Av, size_t plane, int lda, int Kp, const int* __restrict__ seq_off,
                                                            const int* __restrict__ seq_len, int total_rows) {
     const int s = blockIdx.y, p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (p >= seq_len[s] || p > Tpad) return;                     // (wave-uniform)
     const long long row = (long long)seq_off[s] + p;
     if (row < 0 || row >= total_rows) return;
-    float* ap = A + (size_t)row * lda;
     const int K = npers * (MMDM_NF - 4);
     const float* mp = motions + (size_t)s * item_stride + (size_t)(p > 0 ? p - 1 : 0) * row_stride;
     for (int c = lane; c < Kp; c += 64) {
@@ -478,14 +478,26 @@ __global__ __launch_bounds__(256) void motion_pack_kernel(const float* __restric
             const int q = c / (MMDM_NF - 4);
             v = mp[q * MMDM_NF + (c - q * (MMDM_NF - 4))];
         }
-        ap[c] = v;
+        if constexpr (SPLIT) {      // the operand of the fp32-split embedding GEMM: the same element as its two fp16 planes (a zero is +0 in both)
+            _Float16* ap = static_cast<_Float16*>(Av) + (size_t)row * lda;
+            _Float16 hi, lo;
+            mmdm_split2(v, hi, lo);
+            ap[c] = hi;
+            ap[plane + c] = lo;
+        } else {
+            static_cast<float*>(Av)[(size_t)row * lda + c] = v;
+        }
     }
 }
 
 // In place on the embedding GEMM's output h [total_rows, D] (same row walk): the token row becomes query + pe[0], frame row p gets += pe[p]
 // (PositionalEncoding after the token is prepended: src/models/utils/utils.py:37-39).  D % 4 == 0, 16-byte rows.
-__global__ __launch_bounds__(256) void motion_tokens_kernel(float* __restrict__ h, const float* __restrict__ query, const float* __restrict__ pe, int D,
-                                                             const int* __restrict__ seq_off, const int* __restrict__ seq_len, int total_rows) {
+// SPLIT: the rows are layer 0's residual AND the operand of its QKV GEMM in the fp32-split mode, so the same pass writes their two fp16 planes
+// (planes [2][total_rows][D], plane stride in elements) -- the role mdm_pack_split_kernel plays for MDM; h is bitwise the plain form's.
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void motion_tokens_kernel(float* __restrict__ h, _Float16* __restrict__ planes, size_t plane, const float* __restrict__ query,
+                                                             const float* __restrict__ pe, int D, const int* __restrict__ seq_off,
+                                                             const int* __restrict__ seq_len, int total_rows) {
     const int s = blockIdx.y, p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (p >= seq_len[s]) return;                                 // (wave-uniform)
     const long long row = (long long)seq_off[s] + p;
@@ -495,7 +507,8 @@ __global__ __launch_bounds__(256) void motion_tokens_kernel(float* __restrict__ 
     for (int c = lane; c < (D >> 2); c += 64) {
         const f32x4 e = *reinterpret_cast<const f32x4*>(pp + 4 * c);
         const f32x4 a = p == 0 ? *reinterpret_cast<const f32x4*>(query + 4 * c) : *reinterpret_cast<const f32x4*>(hp + 4 * c);
-        *reinterpret_cast<f32x4*>(hp + 4 * c) = a + e;
+        if constexpr (SPLIT) store_row4_split(h, planes, plane, (size_t)row * D + 4 * c, a + e);
+        else *reinterpret_cast<f32x4*>(hp + 4 * c) = a + e;
     }
 }
 
@@ -666,30 +679,45 @@ static int motion_seq_check(const char* who, int nseq, const int* seq_off, const
     return MMDM_OK;
 }
 
-static int motion_pack(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, int lda, int Kp, int nseq, const int* seq_off,
-                       const int* seq_len, int max_len, int total_rows, hipStream_t st) {
+// A (fp32 rows) or planes (the same rows as the two fp16 planes of the fp32-split GEMM's A operand, [2][total_rows][lda], plane stride in elements): exactly one
+static int motion_pack(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, float* A, void* planes, int64_t plane_stride, int lda, int Kp,
+                       int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, hipStream_t st) {
     if (nseq == 0) return MMDM_OK;
     if (int rc = motion_seq_check("mmdm_rowop_motion_pack", nseq, seq_off, seq_len, max_len, total_rows)) return rc;
-    if (!motions || !A || npers < 1 || npers > 2 || Tpad < 0 || row_stride < npers * MMDM_NF || item_stride < (int64_t)Tpad * row_stride ||
+    if (!motions || (A != nullptr) == (planes != nullptr) || npers < 1 || npers > 2 || Tpad < 0 || row_stride < npers * MMDM_NF || item_stride < (int64_t)Tpad * row_stride ||
         Kp < npers * (MMDM_NF - 4) || lda < Kp)
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_pack: bad arguments npers=%d Tpad=%d row stride=%d item stride=%lld Kp=%d lda=%d", npers, Tpad, row_stride,
                               (long long)item_stride, Kp, lda);
+    if (planes && plane_stride < (int64_t)total_rows * lda)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_pack_split: plane stride %lld < total_rows * lda = %lld", (long long)plane_stride, (long long)total_rows * lda);
     if (max_len - 1 > Tpad) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_pack: max_len=%d sequences need %d frames, the buffer holds %d", max_len, max_len - 1, Tpad);
-    hipLaunchKernelGGL(motion_pack_kernel, dim3((max_len + 3) / 4, nseq), dim3(256), 0, st, motions, (long long)item_stride, row_stride, Tpad, npers, A, lda, Kp, seq_off,
-                       seq_len, total_rows);
+    const dim3 grid((max_len + 3) / 4, nseq), block(256);
+    if (planes)
+        hipLaunchKernelGGL(motion_pack_kernel<true>, grid, block, 0, st, motions, (long long)item_stride, row_stride, Tpad, npers, planes, (size_t)plane_stride, lda, Kp,
+                           seq_off, seq_len, total_rows);
+    else
+        hipLaunchKernelGGL(motion_pack_kernel<false>, grid, block, 0, st, motions, (long long)item_stride, row_stride, Tpad, npers, static_cast<void*>(A), (size_t)0, lda, Kp,
+                           seq_off, seq_len, total_rows);
     return mmdm_check_launch("motion_pack");
 }
 
-static int motion_tokens(float* h, const float* query, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len, int max_len,
-                         int total_rows, hipStream_t st) {
+// planes != null: the rows' two fp16 planes [2][total_rows][D] as a second output (plane stride in elements)
+static int motion_tokens(float* h, void* planes, int64_t plane_stride, const float* query, const float* pe, int pe_rows, int D, int nseq, const int* seq_off,
+                         const int* seq_len, int max_len, int total_rows, hipStream_t st) {
     if (nseq == 0) return MMDM_OK;
     if (int rc = motion_seq_check("mmdm_rowop_motion_tokens", nseq, seq_off, seq_len, max_len, total_rows)) return rc;
     if (!h || !query || !pe || D <= 0 || pe_rows <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens: bad arguments D=%d pe_rows=%d", D, pe_rows);
     if ((D & 3) || ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(query) | reinterpret_cast<uintptr_t>(pe)) & 15))
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens: D must be a multiple of 4 and pointers 16-byte aligned");
+    if (planes && (plane_stride < (int64_t)total_rows * D || (plane_stride & 3) || (reinterpret_cast<uintptr_t>(planes) & 7)))
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens_split: planes must be 8-byte aligned with a stride %% 4 == 0 of at least total_rows * D (stride=%lld)",
+                              (long long)plane_stride);
     // the grid's positions are rounded up to whole blocks of 4 waves: every position a wave can take has a pe row
     if ((max_len + 3) / 4 * 4 > pe_rows) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens: max_len=%d needs more than the %d pe rows", max_len, pe_rows);
-    hipLaunchKernelGGL(motion_tokens_kernel, dim3((max_len + 3) / 4, nseq), dim3(256), 0, st, h, query, pe, D, seq_off, seq_len, total_rows);
+    const dim3 grid((max_len + 3) / 4, nseq), block(256);
+    if (planes)
+        hipLaunchKernelGGL(motion_tokens_kernel<true>, grid, block, 0, st, h, static_cast<_Float16*>(planes), (size_t)plane_stride, query, pe, D, seq_off, seq_len, total_rows);
+    else hipLaunchKernelGGL(motion_tokens_kernel<false>, grid, block, 0, st, h, static_cast<_Float16*>(nullptr), (size_t)0, query, pe, D, seq_off, seq_len, total_rows);
     return mmdm_check_launch("motion_tokens");
 }
 
@@ -707,10 +735,18 @@ static int l2_normalize(const float* x, const float* scale, float* out, int rows
     return mmdm_check_launch("l2_normalize");
 }
 
+static int token_embed(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, hipStream_t st) {
+    if (n == 0 || L == 0) return MMDM_OK;
+    if (!table || !tokens || !pos || !out || n < 0 || L < 0 || D <= 0 || vocab <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_token_embed_f32: bad arguments");
+    const size_t total = (size_t)n * L * D;
+    hipLaunchKernelGGL(token_embed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, table, tokens, pos, out, n, L, D, vocab);
+    return mmdm_check_launch("token_embed");
+}
+
 // (host pass only: the device pass would emit a constant of external linkage too, and has no such functions to point at)
 #ifndef __HIP_DEVICE_COMPILE__
 const mmdm_rowops RO(mmdm_rowops_tab) = {adaln_any, layernorm,  layernorm_planes, cond_silu,     cond_silu_planes, mean_time,
-                                         mdm_pack,  mdm_unpack, motion_pack,      motion_tokens, l2_normalize};
+                                         mdm_pack,  mdm_unpack, motion_pack,      motion_tokens, l2_normalize,     token_embed};
 #endif
 
 #ifndef MMDM_ROWOPS_NOPK
@@ -750,11 +786,7 @@ extern "C" int mmdm_mean_time_f32(const float* h, float* out, int nseq, int T, i
 }
 
 extern "C" int mmdm_token_embed_f32(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, void* stream) {
-    if (n == 0 || L == 0) return MMDM_OK;
-    if (!table || !tokens || !pos || !out || n < 0 || L < 0 || D <= 0 || vocab <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_token_embed_f32: bad arguments");
-    const size_t total = (size_t)n * L * D;
-    hipLaunchKernelGGL(token_embed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), table, tokens, pos, out, n, L, D, vocab);
-    return mmdm_check_launch("token_embed");
+    return token_embed(table, vocab, tokens, pos, out, n, L, D, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmdm_influence_head_f32(const float* h, const float* Wout, const float* bout, float* w, int rows, int D, int nw, void* stream) {
@@ -869,14 +901,37 @@ extern "C" int mmdm_rowop_motion_pack(const float* motions, int64_t item_stride,
                                       const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream) {
     const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_motion_pack");
     if (!ro) return MMDM_ERR_ARG;
-    return ro->motion_pack(motions, item_stride, row_stride, Tpad, npers, A, lda, Kp, nseq, seq_off, seq_len, max_len, total_rows, static_cast<hipStream_t>(stream));
+    return ro->motion_pack(motions, item_stride, row_stride, Tpad, npers, A, nullptr, 0, lda, Kp, nseq, seq_off, seq_len, max_len, total_rows, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmdm_rowop_motion_pack_split(const float* motions, int64_t item_stride, int row_stride, int Tpad, int npers, void* planes, int lda, int64_t plane_stride,
+                                            int Kp, int nseq, const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream) {
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_motion_pack_split");
+    if (!ro) return MMDM_ERR_ARG;
+    if (nseq != 0 && !planes) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_pack_split: null planes");
+    return ro->motion_pack(motions, item_stride, row_stride, Tpad, npers, nullptr, planes, plane_stride, lda, Kp, nseq, seq_off, seq_len, max_len, total_rows,
+                           static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmdm_rowop_motion_tokens(float* h, const float* query_token, const float* pe, int pe_rows, int D, int nseq, const int* seq_off, const int* seq_len,
                                         int max_len, int total_rows, int build, void* stream) {
     const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_motion_tokens");
     if (!ro) return MMDM_ERR_ARG;
-    return ro->motion_tokens(h, query_token, pe, pe_rows, D, nseq, seq_off, seq_len, max_len, total_rows, static_cast<hipStream_t>(stream));
+    return ro->motion_tokens(h, nullptr, 0, query_token, pe, pe_rows, D, nseq, seq_off, seq_len, max_len, total_rows, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmdm_rowop_motion_tokens_split(float* h, void* planes, int64_t plane_stride, const float* query_token, const float* pe, int pe_rows, int D, int nseq,
+                                              const int* seq_off, const int* seq_len, int max_len, int total_rows, int build, void* stream) {
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_motion_tokens_split");
+    if (!ro) return MMDM_ERR_ARG;
+    if (nseq != 0 && !planes) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_rowop_motion_tokens_split: null planes");
+    return ro->motion_tokens(h, planes, plane_stride, query_token, pe, pe_rows, D, nseq, seq_off, seq_len, max_len, total_rows, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmdm_rowop_token_embed(const float* table, int vocab, const int* tokens, const float* pos, float* out, int n, int L, int D, int build, void* stream) {
+    const mmdm_rowops* ro = rowops_of(build, "mmdm_rowop_token_embed");
+    if (!ro) return MMDM_ERR_ARG;
+    return ro->token_embed(table, vocab, tokens, pos, out, n, L, D, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mmdm_l2_normalize_rows_f32(const float* x, const float* scale, float* out, int rows, int D, void* stream) {

@@ -21,6 +21,12 @@ item 0, ..., no length sort -- and ``summarize_replications`` / ``f_score_summar
 
 Bitwise: an item's motion embedding does not depend on the batch it is encoded in, on its position in it, or on what the buffer holds beyond
 its length (the reference's own batched result differs from its alone result in the last bits).
+
+Precision: ``InterCLIP(cfg, precision="fp32_split")`` runs both encoders on the fp16 matrix cores at fp32 accuracy (DESIGN section 7's operand format): the
+weight matrices get fp16-plane twins once in ``load_state_dict``, the pack kernels write the embedding operand as planes, ``motion_tokens_split_`` writes
+layer 0's rows and planes, the layers are the library's split post-norm layer (ragged for motions; the text stack's 96-wide heads take its fp32 attention),
+and LayerNorm / Linear / normalise close the path in the row-kernel build a precision-2 sampler handle uses.  ``precision="fp32"`` (the default) is the path
+above, unchanged.  The bitwise statement holds in both modes.
 """
 import numpy as np
 import torch
@@ -34,6 +40,41 @@ EMB_DIM = 512
 TEXT_DIM, TEXT_HEADS, TEXT_LAYERS = 768, 8, 8          # models.py:111-122
 PE_KEY = "motion_encoder.sequence_pos_encoder.pe"
 emb_scale = 6         # metrics.py:8
+PRECISIONS = ("fp32", "fp32_split")
+
+
+def embed_k_pad(npers, precision="fp32"):
+    """Columns of the embedding GEMM's A operand (and of the zero-padded embed weight): npers * 258 rounded up to 16 for the fp32 LDS-DMA GEMM, to 32 for
+    the split GEMM (K % 32 == 0): 528 / 272 and 544 / 288."""
+    m = 32 if precision == "fp32_split" else 16
+    return (int(npers) * (NFEATS - 4) + m - 1) // m * m
+
+
+def split_twin_layout(N, K):
+    """Host: how the fp16-plane twin of an fp32 weight [N, K] is stored -- {"shape": (2, N, K), "plane_stride": N * K, "packed": fragment order or not}.
+    Fragment order wherever the packed split GEMM covers the shape (N % 64 == 0 and K % 64 == 0), plain planes otherwise (the embed weight: K = 544 / 288)."""
+    if K % 32:
+        raise ValueError(f"split twin of a [{N}, {K}] weight: the split GEMM needs K % 32 == 0")
+    return {"shape": (2, int(N), int(K)), "plane_stride": int(N) * int(K), "packed": N % 64 == 0 and K % 64 == 0}
+
+
+def interclip_split_twins(cfg):
+    """Host: name -> split_twin_layout of every weight twin InterCLIP(cfg, precision="fp32_split") builds in load_state_dict: the embed weight zero-padded to
+    Kp, the four GEMM matrices of every motion and text layer (one storage order per layer: fragment order iff D % 64 == 0 and F % 64 == 0), and both output
+    Linears."""
+    D, F, L = int(cfg["LATENT_DIM"]), int(cfg["FF_SIZE"]), int(cfg["NUM_LAYERS"])
+    out = {"motion_encoder.embed_motion.weight": split_twin_layout(D, embed_k_pad(_npers(cfg), "fp32_split"))}
+
+    def stack(prefix, n, d):
+        packed = d % 64 == 0 and F % 64 == 0
+        for i in range(n):
+            for k, (N, K) in (("self_attn.in_proj_weight", (3 * d, d)), ("self_attn.out_proj.weight", (d, d)), ("linear1.weight", (F, d)), ("linear2.weight", (d, F))):
+                out[f"{prefix}layers.{i}.{k}"] = dict(split_twin_layout(N, K), packed=packed)
+    stack("motion_encoder.transformer.", L, D)
+    stack("textTransEncoder.", TEXT_LAYERS, TEXT_DIM)
+    out["motion_encoder.out.weight"] = split_twin_layout(EMB_DIM, D)
+    out["out.weight"] = split_twin_layout(EMB_DIM, TEXT_DIM)
+    return out
 
 
 def strip_model_prefix(state_dict):
@@ -77,9 +118,13 @@ class InterCLIP:
     """InterCLIP(cfg) of src/evaluation/models.py for inference: ``encode_motion`` / ``encode_text`` fill ``batch["motion_emb"]`` /
     ``batch["text_emb"]``.  cfg: the keys of configs/eval.yaml (a mapping or a configs.CfgNode)."""
 
-    def __init__(self, cfg, device="cuda"):
+    def __init__(self, cfg, device="cuda", precision="fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"InterCLIP: precision {precision!r} not recognized ({' / '.join(PRECISIONS)})")
         self.cfg = cfg
         self.device = torch.device(device)
+        self.precision = precision
+        self.split = precision == "fp32_split"
         self.mode = cfg["MODE"]
         self.npers = _npers(cfg)
         if int(cfg["INPUT_DIM"]) != NFEATS - 4:
@@ -88,7 +133,14 @@ class InterCLIP:
             raise ValueError(f"InterCLIP: ACTIVATION {cfg['ACTIVATION']!r} is not supported (gelu)")
         self.D, self.F, self.L, self.H = int(cfg["LATENT_DIM"]), int(cfg["FF_SIZE"]), int(cfg["NUM_LAYERS"]), int(cfg["NUM_HEADS"])
         self.K = self.npers * (NFEATS - 4)
-        self.k_pad = (self.K + 15) // 16 * 16          # the fp32 LDS-DMA GEMM path wants K % 16 == 0: A and the weight are zero-padded alike
+        # the fp32 LDS-DMA GEMM path wants K % 16 == 0, the split GEMM K % 32 == 0: A and the weight are zero-padded alike
+        self.k_pad = embed_k_pad(self.npers, precision)
+        if self.split:
+            if self.D % self.H or self.D // self.H not in (64, 128):
+                raise ValueError(f"InterCLIP: precision 'fp32_split' needs a motion-encoder head size of 64 or 128 (the ragged split layer), got "
+                                 f"LATENT_DIM / NUM_HEADS = {self.D} / {self.H} = head size {self.D / self.H:g}")
+            if self.D % 32 or self.F % 32:
+                raise ValueError(f"InterCLIP: precision 'fp32_split' needs LATENT_DIM and FF_SIZE to be multiples of 32, got {self.D} and {self.F}")
         self._w = None
 
     # ---- weights -------------------------------------------------------------------------------------------------------------------
@@ -122,6 +174,12 @@ class InterCLIP:
         ew[:, :self.K] = g("motion_encoder.embed_motion.weight")
         w["embed_w"] = ew
         w["pe"] = pe_table(self.D, max_len=2000).to(self.device).contiguous()          # MotionEncoder: PositionalEncoding(max_len=2000)
+        if self.split:          # the fp16-plane twins, once: embed (plain planes: Kp % 64 != 0), the layers and both output Linears
+            w["embed_s"] = ops.split_weight(ew, pack=False)[0]
+            w["m_layers_s"] = [ops.encoder_layer_split_weights(lw) for lw in w["m_layers"]]
+            w["t_layers_s"] = [ops.encoder_layer_split_weights(lw) for lw in w["t_layers"]]
+            w["m_out_s"], w["m_out_packed"] = ops.split_weight(w["m_out_w"])
+            w["t_out_s"], w["t_out_packed"] = ops.split_weight(w["t_out_w"])
         self._w = w
         return self
 
@@ -163,6 +221,19 @@ class InterCLIP:
         emb = ops.linear(tok, w["m_out_w"], w["m_out_b"])
         return ops.l2_normalize(emb, w["scale"])
 
+    def _encode_packed_split(self, a, seq_off, seq_len, total, longest):
+        """_encode_packed in the fp32_split mode: a = the A operand as fp16 planes [2, total, k_pad].  Row kernels: build 1 (what a precision-2 handle runs)."""
+        w = self._weights()
+        h = ops.linear_split(a, w["embed_s"], w["embed_b"])
+        h, hs = ops.motion_tokens_split_(h, w["query"], w["pe"], seq_off, seq_len, longest, build=1)
+        ws = torch.empty(ops.load_library().mmdm_encoder_layer_split_workspace(1, total, self.D, self.F), device=self.device, dtype=torch.float32)
+        for i, lw in enumerate(w["m_layers_s"]):
+            ops.encoder_layer_ragged_split_(h, hs, lw, self.H, seq_off, seq_len, longest, eps=1e-5, last=i + 1 == self.L, workspace=ws)
+        tok = ops.gather_rows(h, seq_off)
+        _, toks = ops.layernorm_split(tok, w["out_ln_w"], w["out_ln_b"], 1e-5, build=1)
+        emb = ops.linear_split(toks, w["m_out_s"], w["m_out_b"], packed=w["m_out_packed"])
+        return ops.l2_normalize(emb, w["scale"], build=1)
+
     def encode_motion(self, batch):
         """batch["motions"] [B, T, npers * 262], batch["motion_lens"] [B] -> batch["motion_emb"] [B, 512] (models.py:144-154, 50-80)."""
         self._weights()
@@ -171,6 +242,10 @@ class InterCLIP:
             raise ValueError(f"encode_motion: {motions.shape[0]} motions but {len(off_h)} lengths")
         seq_off = torch.from_numpy(off_h).to(self.device)
         seq_len = torch.from_numpy(len_h).to(self.device)
+        if self.split:
+            a = ops.motion_pack_split(motions, seq_off, seq_len, longest, total, npers=self.npers, k_pad=self.k_pad, build=1)
+            batch["motion_emb"] = self._encode_packed_split(a, seq_off, seq_len, total, longest)
+            return batch
         a = ops.motion_pack(motions, seq_off, seq_len, longest, total, npers=self.npers, k_pad=self.k_pad)
         batch["motion_emb"] = self._encode_packed(a, seq_off, seq_len, total, longest)
         return batch
@@ -193,6 +268,10 @@ class InterCLIP:
         total = int(len_h.sum())
         seq_off = torch.from_numpy(off_h).to(self.device)
         seq_len = torch.from_numpy(len_h).to(self.device)
+        if self.split:
+            a = ops.center_pack_split(motions, seq_off, seq_len, longest, total, k_pad=self.k_pad)
+            batch["motion_emb"] = self._encode_packed_split(a, seq_off, seq_len, total, longest)
+            return batch
         a = ops.center_pack(motions, seq_off, seq_len, longest, total, k_pad=self.k_pad)
         batch["motion_emb"] = self._encode_packed(a, seq_off, seq_len, total, longest)
         return batch
@@ -204,7 +283,16 @@ class InterCLIP:
         w = self._weights()
         tokens = torch.as_tensor(batch["tokens_text"]) if "tokens_text" in batch else tokenize(list(batch["text"]))
         tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
-        x = ops.token_embed(w["table"], tok, w["pos"])
+        x = ops.token_embed(w["table"], tok, w["pos"], build=1 if self.split else 0)
+        if self.split:          # the uniform split layer; 768 / 8 = 96-wide heads: its fp32 attention.  The planes of the embedded tokens are layer 0's operand.
+            xs = ops.split_f32(x)
+            ws = torch.empty(ops.load_library().mmdm_encoder_layer_split_workspace(x.shape[0], x.shape[1], TEXT_DIM, self.F), device=self.device, dtype=torch.float32)
+            for i, lw in enumerate(w["t_layers_s"]):
+                ops.encoder_layer_split_(x, xs, lw, TEXT_HEADS, eps=1e-5, last=i + 1 == TEXT_LAYERS, workspace=ws)
+            _, eots = ops.layernorm_split(_eot_rows(tokens, x), w["text_ln_w"], w["text_ln_b"], 1e-5, build=1)      # LayerNorm is per row: the EOT rows only
+            out = ops.linear_split(eots, w["t_out_s"], w["t_out_b"], packed=w["t_out_packed"])
+            batch["text_emb"] = ops.l2_normalize(out, w["scale"], build=1)
+            return batch
         ws = None
         for lw in w["t_layers"]:
             ops.encoder_layer_(x, lw, TEXT_HEADS, norm_first=False, activation="gelu", causal=False, eps=1e-5, workspace=ws)
@@ -216,15 +304,15 @@ class InterCLIP:
 
 class EvaluatorModelWrapper:
     """EvaluatorModelWrapper of src/evaluation/utils.py:126-235.  cfg_or_model: an InterCLIP with its weights loaded, or a cfg whose CHECKPOINT
-    names a checkpoint file (loaded as build_models does)."""
+    names a checkpoint file (loaded as build_models does; ``precision`` is InterCLIP's and applies to that case only: a model handed in keeps its own)."""
 
-    def __init__(self, cfg_or_model, device="cuda"):
+    def __init__(self, cfg_or_model, device="cuda", precision="fp32"):
         if isinstance(cfg_or_model, InterCLIP):
             self.model = cfg_or_model
         else:
             cfg = cfg_or_model
             ckpt = torch.load(cfg["CHECKPOINT"], map_location="cpu")
-            self.model = InterCLIP(cfg, device=device).load_state_dict(strip_model_prefix(ckpt["state_dict"]), strict=True)
+            self.model = InterCLIP(cfg, device=device, precision=precision).load_state_dict(strip_model_prefix(ckpt["state_dict"]), strict=True)
         self.cfg = self.model.cfg
         self.device = self.model.device
         self.extended = bool(self.cfg.get("EXTENDED", False))
@@ -267,13 +355,13 @@ class EvaluatorModelWrapperIndividual:
     p2 of item 0, p1 of item 1, ...; the centring is InterCLIP.encode_motion_individual's (over the whole buffer handed in)."""
     individual = True
 
-    def __init__(self, cfg_or_model, device="cuda"):
+    def __init__(self, cfg_or_model, device="cuda", precision="fp32"):
         if isinstance(cfg_or_model, InterCLIP):
             self.model = cfg_or_model
         else:
             cfg = cfg_or_model
             ckpt = torch.load(cfg["CHECKPOINT"], map_location="cpu")
-            self.model = InterCLIP(cfg, device=device).load_state_dict(strip_model_prefix(ckpt["state_dict"]), strict=True)
+            self.model = InterCLIP(cfg, device=device, precision=precision).load_state_dict(strip_model_prefix(ckpt["state_dict"]), strict=True)
         if self.model.mode != "individual":
             raise ValueError(f"EvaluatorModelWrapperIndividual: the model's MODE is {self.model.mode!r}; it needs MODE 'individual'")
         self.cfg = self.model.cfg

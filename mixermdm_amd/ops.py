@@ -6,7 +6,7 @@ tensor.  No function here computes anything in Python: a non-CUDA tensor raises.
 import ctypes as C
 import torch
 
-from ._lib import load_library, check, EncoderLayerWeights
+from ._lib import load_library, check, EncoderLayerWeights, EncoderLayerSplitWeights
 
 EPI = {"bias": 0, "gelu": 1, "resid": 2, "pe": 3, "silu": 4, "quickgelu": 5, "sigmoid": 6}
 ATTN_NO_ZERO_KEY, ATTN_CAUSAL = 1, 2
@@ -147,15 +147,18 @@ def layernorm_split(x, weight, bias, eps=1e-5, build=0, planes=True):
     return out, (buf[:, :n].reshape(2, *x.shape) if planes else None)
 
 
-def token_embed(table, tokens, pos):
-    """table[tokens] + pos[:L]; tokens int32 [n, L] on the device."""
+def token_embed(table, tokens, pos, build=0):
+    """table[tokens] + pos[:L]; tokens int32 [n, L] on the device.  build as in `adaln`."""
     _chk(table, tokens, pos)
     assert tokens.dtype == torch.int32 and tokens.is_contiguous() and table.is_contiguous() and pos.is_contiguous()
     n, L = tokens.shape
     D = table.shape[1]
     assert pos.shape[0] >= L and pos.shape[1] == D
     out = torch.empty(n, L, D, device=table.device, dtype=torch.float32)
-    check(load_library().mmdm_token_embed_f32(_p(table), table.shape[0], _p(tokens), _p(pos), _p(out), n, L, D, _stream()))
+    if build == 0:
+        check(load_library().mmdm_token_embed_f32(_p(table), table.shape[0], _p(tokens), _p(pos), _p(out), n, L, D, _stream()))
+    else:
+        check(load_library().mmdm_rowop_token_embed(_p(table), table.shape[0], _p(tokens), _p(pos), _p(out), n, L, D, int(build), _stream()))
     return out
 
 
@@ -283,6 +286,136 @@ def center_pack(motions, seq_off, seq_len, max_len, total_rows, k_pad=None, out=
     check(load_library().mmdm_center_pack_f32(_p(motions), motions.stride(0), motions.stride(1), motions.shape[1], motions.shape[0], _p(out), out.stride(0), k_pad,
                                               po, pl, int(max_len), int(total_rows), _p(floor_ws), _stream()))
     return out
+
+
+def _planes_out(out, rows, ld, device):
+    """A contiguous float16 [2, n] buffer whose row length n is the plane stride (n >= rows * ld, a multiple of 8); created unless given."""
+    if out is None:
+        out = torch.empty(2, (rows * ld + 7) // 8 * 8, device=device, dtype=torch.float16)
+    assert out.is_cuda and out.dtype == torch.float16 and out.dim() == 2 and out.shape[0] == 2 and out.is_contiguous() and out.shape[1] >= rows * ld
+    return out
+
+
+def split_k_pad(npers):
+    """Columns of the evaluator's embedding operand in the fp32_split mode: npers * 258 rounded up to a multiple of 32 (the split GEMM needs K % 32 == 0):
+    544 for two persons, 288 for one."""
+    return (int(npers) * 258 + 31) // 32 * 32
+
+
+def motion_pack_split(motions, seq_off, seq_len, max_len, total_rows, npers=2, k_pad=None, build=1, out=None):
+    """motion_pack written directly as the two fp16 planes of the split embedding GEMM's A operand (mmdm_rowop_motion_pack_split): returns float16
+    [2, total_rows, k_pad], bitwise split_f32 of motion_pack's result in the rows of the sequences (pad columns and token rows +0 in both planes); other
+    rows are left as they are in `out` (a contiguous float16 [2, n >= total_rows * k_pad] buffer; new: uninitialised).  k_pad: split_k_pad(npers) unless given."""
+    _chk(motions)
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    assert motions.dim() == 3 and motions.stride(2) == 1 and motions.shape[0] == nseq and motions.shape[2] == npers * 262
+    k_pad = split_k_pad(npers) if k_pad is None else int(k_pad)
+    out = _planes_out(out, total_rows, k_pad, motions.device)
+    check(load_library().mmdm_rowop_motion_pack_split(_p(motions), motions.stride(0), motions.stride(1), motions.shape[1], int(npers), _p(out), k_pad, out.shape[1],
+                                                      k_pad, nseq, po, pl, int(max_len), int(total_rows), int(build), _stream()))
+    return out[:, :total_rows * k_pad].unflatten(1, (total_rows, k_pad))
+
+
+def center_pack_split(motions, seq_off, seq_len, max_len, total_rows, k_pad=None, out=None):
+    """center_pack written directly as the two fp16 planes of the split embedding GEMM's A operand (mmdm_center_pack_split): float16 [2, total_rows, k_pad],
+    bitwise split_f32 of center_pack's result in the rows of the sequences.  k_pad: 288 unless given; `out` as in motion_pack_split."""
+    _chk(motions)
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    assert motions.dim() == 3 and motions.stride(2) == 1 and motions.shape[2] == 524 and nseq == 2 * motions.shape[0]
+    k_pad = split_k_pad(1) if k_pad is None else int(k_pad)
+    out = _planes_out(out, total_rows, k_pad, motions.device)
+    floor_ws = torch.empty(max(nseq, 1), device=motions.device, dtype=torch.float32)
+    check(load_library().mmdm_center_pack_split(_p(motions), motions.stride(0), motions.stride(1), motions.shape[1], motions.shape[0], _p(out), k_pad, out.shape[1], k_pad,
+                                                po, pl, int(max_len), int(total_rows), _p(floor_ws), _stream()))
+    return out[:, :total_rows * k_pad].unflatten(1, (total_rows, k_pad))
+
+
+def motion_tokens_split_(h, query_token, pe, seq_off, seq_len, max_len, build=1, planes=None):
+    """motion_tokens_ that also writes the rows' two fp16 planes in the same pass (mmdm_rowop_motion_tokens_split): IN PLACE on h [total_rows, D], returns
+    (h, planes float16 [2, total_rows, D]) with planes == split_f32(h) in the rows of the sequences.  planes: a contiguous float16 [2, n >= total_rows * D]
+    buffer (n = the plane stride), created unless given."""
+    _chk(h, query_token, pe)
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    assert h.dim() == 2 and h.is_contiguous() and pe.dim() == 2 and pe.is_contiguous() and query_token.is_contiguous()
+    rows, D = h.shape
+    assert pe.shape[1] == D and query_token.numel() == D
+    planes = _planes_out(planes, rows, D, h.device)
+    check(load_library().mmdm_rowop_motion_tokens_split(_p(h), _p(planes), planes.shape[1], _p(query_token), _p(pe), pe.shape[0], D, nseq, po, pl, int(max_len), rows,
+                                                        int(build), _stream()))
+    return h, planes[:, :rows * D].unflatten(1, (rows, D))
+
+
+_SPLIT_LAYER_NAMES = ("in_proj_weight", "out_proj.weight", "linear1.weight", "linear2.weight", "in_proj_bias", "out_proj.bias", "linear1.bias", "linear2.bias",
+                      "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")
+
+
+def split_weight(w, pack=None):
+    """The fp16-plane twin of an fp32 weight [N, K] for linear_split: (float16 [2, N, K], packed) -- split_f32 of it, in fragment order (split_pack_weight)
+    when `pack` (default: whenever the packed kernel covers the shape, N % 64 == 0 and K % 64 == 0; results are bit-identical either way)."""
+    _chk(w)
+    assert w.dim() == 2
+    N, K = w.shape
+    if pack is None:
+        pack = N % 64 == 0 and K % 64 == 0
+    ws = split_f32(w)
+    return (split_pack_weight(ws), True) if pack else (ws, False)
+
+
+def encoder_layer_split_weights(w, pack=None):
+    """The weights of encoder_layer_split_ / encoder_layer_ragged_split_ from the fp32 dict of encoder_layer_: the four GEMM matrices as fp16 planes -- all in
+    fragment order when `pack` (default: D % 64 == 0 and F % 64 == 0), all plain otherwise -- the biases and norms as they are.  Returns a dict with the
+    names of encoder_layer_ plus "packed"."""
+    F, D = w["linear1.weight"].shape
+    if pack is None:
+        pack = D % 64 == 0 and F % 64 == 0
+    out = {k: w[k].contiguous() for k in _SPLIT_LAYER_NAMES[4:]}
+    for k in _SPLIT_LAYER_NAMES[:4]:
+        out[k] = split_weight(w[k].contiguous(), pack)[0]
+    out["packed"] = bool(pack)
+    return out
+
+
+def _split_layer_args(x, xs, w):
+    ts = [w[k] for k in _SPLIT_LAYER_NAMES]
+    _chk(x, *ts[4:])
+    for t in ts[:4]:
+        if not t.is_cuda or t.dtype != torch.float16 or t.dim() != 3 or t.shape[0] != 2 or not t.is_contiguous():
+            raise TypeError("encoder_layer_split_: the GEMM weights are contiguous CUDA float16 [2, N, K] planes (ops.encoder_layer_split_weights)")
+    if not xs.is_cuda or xs.dtype != torch.float16 or xs.shape[0] != 2 or xs.stride(-1) != 1 or tuple(xs.shape[1:]) != tuple(x.shape):
+        raise TypeError("encoder_layer_split_: xs is the float16 planes [2, *x.shape] of x (ops.split_f32)")
+    assert x.is_contiguous() and xs[0].is_contiguous() and xs[1].is_contiguous() and all(t.is_contiguous() for t in ts)
+    return EncoderLayerSplitWeights(*[t.data_ptr() for t in ts], int(bool(w["packed"]))), w["linear1.weight"].shape[1]
+
+
+def encoder_layer_split_(x, xs, w, num_heads, norm_first=False, eps=1e-5, last=False, workspace=None):
+    """One post-norm nn.TransformerEncoderLayer (gelu) on SPLIT operands, x [nseq, T, D] fp32 IN PLACE and xs, its float16 planes [2, nseq, T, D], rewritten
+    for the next layer (mmdm_encoder_layer_split; last=True skips the final plane write).  w: ops.encoder_layer_split_weights.  Head sizes 64 / 128 run the
+    two-plane attention, any other <= 256 the fp32 attention.  Returns x."""
+    cw, F = _split_layer_args(x, xs, w)
+    nseq, T, D = x.shape
+    lib = load_library()
+    need = lib.mmdm_encoder_layer_split_workspace(nseq, T, D, F)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=x.device, dtype=torch.float32)
+    check(lib.mmdm_encoder_layer_split(_p(x), _p(xs), xs.stride(0), C.byref(cw), nseq, T, D, num_heads, F, int(norm_first), float(eps), int(last),
+                                       _p(workspace), workspace.numel(), _stream()))
+    return x
+
+
+def encoder_layer_ragged_split_(x, xs, w, num_heads, seq_off, seq_len, max_len, norm_first=False, eps=1e-5, last=False, workspace=None):
+    """encoder_layer_split_ on a ragged batch, x [total_rows, D] and xs [2, total_rows, D] IN PLACE (mmdm_encoder_layer_ragged_split): sequences as in
+    encoder_layer_ragged_; every sequence's rows are bitwise those of encoder_layer_split_ on that sequence alone.  Head sizes 64 / 128."""
+    cw, F = _split_layer_args(x, xs, w)
+    assert x.dim() == 2
+    nseq, po, pl = _seq_args(seq_off, seq_len)
+    rows, D = x.shape
+    lib = load_library()
+    need = lib.mmdm_encoder_layer_split_workspace(1, rows, D, F)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=x.device, dtype=torch.float32)
+    check(lib.mmdm_encoder_layer_ragged_split(_p(x), _p(xs), xs.stride(0), C.byref(cw), nseq, po, pl, int(max_len), rows, D, num_heads, F, int(norm_first),
+                                              float(eps), int(last), _p(workspace), workspace.numel(), _stream()))
+    return x
 
 
 def l2_normalize(x, scale, build=0):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the InterCLIP INDIVIDUAL evaluator (InterCLIP.encode_motion_individual, mixermdm_amd/evaluation.py) at full size on an MI355X.
 
-    python tools/evaluator_individual_bench.py [--items 64] [--batch 32] [--repeats 20] [--warmup 3] [--out profiles/evaluator_individual_bench.json]
+    python tools/evaluator_individual_bench.py [--items 64] [--batch 32] [--repeats 20] [--warmup 3] [--precision fp32] [--out profiles/evaluator_individual_bench.json]
 
 The workload of tools/evaluator_bench.py -- `--items` interactions with T uniform in [60, 300] (seeded), batches of `--batch` -- through
 configs/eval_individual.yaml (D = 1024, 8 heads, F = 2048, 8 layers, one person per sequence) with synthetic weights: every item gives two embeddings.
@@ -12,6 +12,9 @@ After the warm-up every repeat encodes all items and ends in a device synchronis
                                             the same batches: ms per batch and its share of the encode
   unfused                                   context, no gate: the same batches with ops.center_motion + the batch-level interleave + ops.motion_pack(npers=1)
                                             in front of the same encoder -- ms per batch of that front end alone and of the whole encode
+
+--precision fp32_split measures InterCLIP(cfg, precision="fp32_split"): the fused front end is ops.center_pack_split, the unfused one ends in
+ops.motion_pack_split, both in front of the split encoder (default output then: profiles/evaluator_individual_bench_split.json).
 
 One JSON line on stdout; also written to --out.  There is no CPU fall-back: without a GPU the tool fails.
 """
@@ -33,8 +36,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "evaluator_individual_bench.json"))
+    ap.add_argument("--precision", choices=("fp32", "fp32_split"), default="fp32")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    split = args.precision == "fp32_split"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "evaluator_individual_bench_split.json" if split else "evaluator_individual_bench.json")
     import numpy as np
     import torch
     if not torch.cuda.is_available():
@@ -48,7 +55,7 @@ def main():
     gen = torch.Generator().manual_seed(args.seed)
     sd = {k: torch.randn(s, generator=gen) * 0.02 for k, s in interclip_shapes(cfg, vocab=64, context=77).items()}
     sd["latent_scale"] = torch.ones(1)
-    model = InterCLIP(cfg, device=dev).load_state_dict(sd)
+    model = InterCLIP(cfg, device=dev, precision=args.precision).load_state_dict(sd)
     rng = np.random.RandomState(args.seed)
     lens = rng.randint(60, 301, size=args.items).tolist()
     batches = []
@@ -61,12 +68,16 @@ def main():
 
     def front_fused(b):
         motions, _, so, sl, total, longest = b
+        if split:
+            return ops.center_pack_split(motions, so, sl, longest, total, k_pad=model.k_pad)
         return ops.center_pack(motions, so, sl, longest, total, k_pad=model.k_pad)
 
     def front_unfused(b):
         motions, _, so, sl, total, longest = b
         B, T, _ = motions.shape
         centred = ops.center_motion(motions).reshape(B, T, 2, 262).transpose(1, 2).reshape(2 * B, T, 262)
+        if split:
+            return ops.motion_pack_split(centred, so, sl, longest, total, npers=1, k_pad=model.k_pad, build=1)
         return ops.motion_pack(centred, so, sl, longest, total, npers=1, k_pad=model.k_pad)
 
     def run(fused):
@@ -75,7 +86,7 @@ def main():
             if fused:
                 out = model.encode_motion_individual({"motions": b[0], "motion_lens": b[1]})["motion_emb"]
             else:
-                out = model._encode_packed(front_unfused(b), b[2], b[3], b[4], b[5])
+                out = (model._encode_packed_split if split else model._encode_packed)(front_unfused(b), b[2], b[3], b[4], b[5])
         torch.cuda.synchronize()
         return out
 
@@ -110,7 +121,7 @@ def main():
     same = bool(torch.equal(run(True), run(False)))
     med = lambda v: float(np.median(v))
     nb = len(batches)
-    line = {"metric": "evaluator_individual_embeddings_per_s", "value": round(2 * args.items / med(t_fused), 1), "unit": "embeddings/s", "precision": "fp32",
+    line = {"metric": "evaluator_individual_embeddings_per_s", "value": round(2 * args.items / med(t_fused), 1), "unit": "embeddings/s", "precision": args.precision,
             "items": args.items, "embeddings": 2 * args.items, "batch": args.batch, "frames": [min(lens), max(lens)], "repeats": len(t_fused),
             "warmup": args.warmup, "ms_per_batch": round(1e3 * med(t_fused) / nb, 3),
             "ms_per_pass_min_max": [round(1e3 * min(t_fused), 3), round(1e3 * max(t_fused), 3)],
@@ -120,7 +131,7 @@ def main():
             "unfused": {"front_ms_per_batch": round(1e3 * med(c_unfused) / nb, 4), "ms_per_batch": round(1e3 * med(t_unfused) / nb, 3),
                         "embeddings_per_s": round(2 * args.items / med(t_unfused), 1),
                         "what": "center_motion + batch-level interleave + motion_pack(npers=1) in front of the same encoder: context, not a gate"},
-            "device": torch.cuda.get_device_name(0), "kernel_sources_sha": sources_sha("fp32")}
+            "device": torch.cuda.get_device_name(0), "kernel_sources_sha": sources_sha(args.precision)}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(line, f, indent=1)
