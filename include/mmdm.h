@@ -500,7 +500,16 @@ typedef struct {
                         *    ClassifierFreeSampleModelMultiple  src/models/utils/cfg_sampler.py:59-98; in2in.py:330-341)
                         * 3: single chain, in2IN "dual": denoiser1 in "dual_individual" and denoiser2 in "dual_interaction" mode composed by
                         *    ClassifierFreeSampleDualMDM  cfg_sampler.py:101-150, in2in.py:318-329; cond [B, 5*text_dim]; guidance scales
-                        *    cfg_scale_individual / cfg_scale_interaction; needs mmdm_set_dual_weights */
+                        *    cfg_scale_individual / cfg_scale_interaction; needs mmdm_set_dual_weights
+                        * 4: single chain, the InterGen denoiser alone under the 2-way CFG: InterDiffusion.forward_test / InterGen  src/models/intergen.py:20-213,
+                        *    ClassifierFreeSampleModel  cfg_sampler.py:12-28.  Denoiser 2 only, model2_kind must be 1 (anything else is MMDM_ERR_ARG); cond
+                        *    [B, text_dim] (doubled to 2B rows with a zero uncond half; ONE text embedding per CFG row conditions every norm of both persons,
+                        *    intergen.py:266-270), x [B, T, 524], guidance scale cfg_scale; every precision mode.  The one single-chain mode that takes the
+                        *    loop's other arguments (GaussianDiffusion.ddim_sample_loop_progressive  gaussian_diffusion.py:999-1069): mmdm_set_eta,
+                        *    mmdm_begin_opts and mmdm_begin_ragged_opts with the argument rules of the two-chain sampler -- the step noise [.., 524] is added to
+                        *    the one chain, x_start pins columns 0, 2, 262, 264 of it, init_image / skip_timesteps start it from q_sample.  mmdm_begin_ragged
+                        *    covers it at head sizes 64 / 128; mmdm_set_key_mask and mmdm_set_history (with a destination) refuse it; mmdm_copy_result /
+                        *    mmdm_get_state give pred_xstart [B, T, 524]; mmdm_module_forward takes which = 1 */
     float cfg_scale_interaction, cfg_scale_individual;   /* CFG_WEIGHT_INTERACTION / CFG_WEIGHT_INDIVIDUAL (single_only == 2) */
     int precision;     /* 0: exact fp32 everywhere (the parity path).  1: bf16 operands for the transformer-stack GEMMs (weights
                         *    converted once at mmdm_prepare; AdaLN / attention / GELU outputs written as bf16), fp32 accumulation,
@@ -573,14 +582,15 @@ int mmdm_set_schedule(mmdm_handle h, const int* timestep_map, const float* coef,
  * step (ClassifierFreeSampleDualMDM.weight, cfg_sampler.py:113-125).  Call after every mmdm_set_schedule. */
 int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S);
 
-/* Stochastic DDIM (eta > 0; two-chain sampler only): coef_eta_host [2*S] HOST floats = sqrt(1 - ab_prev - sigma^2) and sigma of every respaced
+/* Stochastic DDIM (eta > 0; the two-chain sampler and the stand-alone InterGen sampler, single_only 0 / 4): coef_eta_host [2*S] HOST floats = sqrt(1 - ab_prev - sigma^2) and sigma of every respaced
  * step, sigma = eta sqrt((1 - ab_prev) / (1 - ab)) sqrt(1 - ab / ab_prev) in fp32 (gaussian_diffusion.py:1939-1951); NULL clears it (S ignored)
  * and the update is the eta = 0 one again.  Call after mmdm_set_schedule, which resets it; it ends a begun call.  While a table is set every
  * begin must name a noise source (mmdm_begin_opts, or mmdm_begin_ragged_opts for a ragged batch; MMDM_ERR_STATE otherwise -- so mmdm_begin is refused;
  * the option-less mmdm_begin_ragged is MMDM_ERR_UNSUPPORTED and points at mmdm_begin_ragged_opts); a noise source without a table is MMDM_ERR_STATE as
  * well.  The step then ends in
  *   x = x0 sqrt(ab_prev) + coef_eta[0][i] eps + [i != 0] coef_eta[1][i] noise        (both chains, the SAME noise [B, T, 524]; :1947-1963)
- * The call waits for the stream of the handle's last begin before it replaces the table.  single_only != 0: MMDM_ERR_UNSUPPORTED. */
+ * The call waits for the stream of the handle's last begin before it replaces the table.  single_only 1 / 2 / 3: MMDM_ERR_UNSUPPORTED.
+ * single_only = 4: the one chain ends in the same form (gaussian_diffusion.py:836-848). */
 int mmdm_set_eta(mmdm_handle h, const float* coef_eta_host, int S);
 
 /* Check that every weight is present; allocate nothing afterwards. */
@@ -604,7 +614,7 @@ int mmdm_prepare(mmdm_handle h);
  * Precision 0 and 2 (fp32_split) handles take a mask: the fp32 attention kernel and the two-plane kernel of the fp32-split mode each have a masked
  * instantiation (mmdm_attention_masked_f32, mmdm_attention_split_masked), and a precision-2 stack whose head size is not 64 / 128 runs the fp32 one.
  * MMDM_ERR_UNSUPPORTED (never a silent unmasked run): precision 1 and 3 handles (the bf16 attention forms take no mask), model1_kind = 1 (the
- * MDM encoder's src_key_padding_mask, in either precision), single_only 2 / 3 (and so which = 3); with a mask set, mmdm_begin_ragged is
+ * MDM encoder's src_key_padding_mask, in either precision), single_only 2 / 3 / 4 (and so which = 3); with a mask set, mmdm_begin_ragged is
  * MMDM_ERR_UNSUPPORTED. */
 int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, int T);
 
@@ -612,7 +622,8 @@ int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, 
  * x_T [B,T,524] (or [B,T,262]); both chains start from x_T (gaussian_diffusion.py:1863).  Precomputes the text embeddings. */
 int mmdm_begin(mmdm_handle h, const float* cond, const float* x_T, int B, int T, void* stream);
 
-/* mmdm_begin with the loop's other arguments (MixerDiffusion.ddim_sample_loop_progressive, gaussian_diffusion.py:1822-1899); two-chain sampler,
+/* mmdm_begin with the loop's other arguments (MixerDiffusion.ddim_sample_loop_progressive, gaussian_diffusion.py:1822-1899); two-chain sampler
+ * and the stand-alone InterGen sampler (single_only = 4: read "the chain" for "both chains" below; gaussian_diffusion.py:999-1069),
  * uniform batches (ragged ones: mmdm_begin_ragged_opts).  A zeroed struct (or opts == NULL) is mmdm_begin.  Options belong to the CALL: every mmdm_begin / mmdm_begin_ragged resets
  * them, as it resets the history.  Device buffers are the caller's and must stay alive until the stream has passed the call's last step.
  *   noise_source  0 = none; 1 = `noise` [noise_steps, B, T, 524]: slot k is th.randn_like(x) of the step at loop position k (0 = the first executed
@@ -659,10 +670,10 @@ int mmdm_begin_opts(mmdm_handle h, const float* cond, const float* x_T, int B, i
  * [rows, 524] buffers whose first sum(lens) rows are the items back to back; history slots (mmdm_set_history) are [2 * rows, C] with the
  * uncond half at row `rows`; mmdm_call_rows returns (rows, sum(lens)).  Covers the two-chain sampler and the single-person sampler over
  * in2IN / InterGen denoisers with head sizes 64 / 128, every precision mode, and over MDMDenoiser as denoiser 1 (head sizes 64 / 128, fp32 and
- * fp32-split: the precisions MDM has); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
+ * fp32-split: the precisions MDM has), and the stand-alone InterGen sampler (single_only = 4); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
  * otherwise MMDM_ERR_UNSUPPORTED / MMDM_ERR_ARG.  mmdm_run / mmdm_seek / mmdm_set_history as after mmdm_begin. */
 int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, void* stream);
-/* mmdm_begin_ragged with the loop's other arguments: mmdm_begin_opts for a RAGGED batch (two-chain sampler; every precision mode; in2IN / InterGen
+/* mmdm_begin_ragged with the loop's other arguments: mmdm_begin_opts for a RAGGED batch (two-chain sampler and single_only = 4; every precision mode; in2IN / InterGen
  * denoisers and MDM as denoiser 1 where ragged batches cover it).  The rule of ragged batches holds with every option: each item is BIT-IDENTICAL to
  * the same item sampled alone with the same options (tests/test_gpu_ragged_opts.py).  A zeroed struct (or opts == NULL) is mmdm_begin_ragged.  Device
  * buffers are PACKED like x_T -- the items' frames back to back -- are the caller's and must stay alive until the stream has passed the call's last
@@ -679,7 +690,7 @@ int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B,
  * keyed by (noise_source, x_start given) beside the ragged key (B, rows, query tiles of the longest item, S) -- other values and other lengths of the
  * same bucket replay the same graph, another form never does.  mmdm_run's check against the noise buffer and mmdm_seek behave as after mmdm_begin_opts.
  * MMDM_ERR_STATE: eta table and noise source not both present / both absent.  MMDM_ERR_ARG: noise_steps < S - skip_timesteps, skip_timesteps outside
- * [0, S), noise_source 2 without item_seed.  MMDM_ERR_UNSUPPORTED: single_only != 0 with any option set; a key mask on the handle. */
+ * [0, S), noise_source 2 without item_seed.  MMDM_ERR_UNSUPPORTED: single_only 1 / 2 / 3 with any option set; a key mask on the handle. */
 typedef struct {
     int noise_source;
     int noise_steps;

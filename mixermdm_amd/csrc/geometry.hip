@@ -578,14 +578,61 @@ __global__ __launch_bounds__(256) void center_pack_kernel(const float* __restric
     }
 }
 
+// ClassifierFreeSampleModel combine + single-chain DDIM update on rows of any width C (262: one person, 524: two).  The forms of xstart_ddim_kernel:
+// NOISE 0 = the deterministic update (no extra argument: the kernel the single-chain samplers have always launched), 1 = + sigma * noise[loop_pos] from the
+// caller's buffer [n_steps, per_batch_total], 2 = + sigma * step_normal(seed, loop_pos, b, t, column) -- the generator's counter is (t * 524 + column, b, lp)
+// whatever C is, so what mmdm_randn_f32 writes is what a 524-wide chain draws.  Forms 1 / 2 take sqrt(1 - ab_prev - sigma^2) and sigma from the eta table
+// and add no noise at i = 0 (gaussian_diffusion.py:840-848).  RAG: the chain is a group of rg.rows frame rows (padding rows return: they stay zero), the
+// uncond half of m lies per_batch_total = rg.rows * C further on, a slot of the packed noise buffer is noise_stride elements (descriptor) and the generator is
+// keyed per item by (item_seed[b], item_noise_row[b]).
+struct CfgRows { int T, C; mmdm_rag rg; };          // what every form but <false, 0> takes beside the plain arguments: the rows' coordinates
+__device__ __forceinline__ const CfgRows& cfg_rows_of(const CfgRows& r) { return r; }
+__device__ __forceinline__ const CfgRows& cfg_rows_of(const CfgRows& r, const NoiseArgs&) { return r; }
+__device__ __forceinline__ const NoiseArgs& cfg_noise_of(const CfgRows&, const NoiseArgs& a) { return a; }
+template <bool RAG = false, int NOISE = 0, typename... NA>
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__ m, const float* __restrict__ coef, int S, const int* __restrict__ step_idx,
-                                                        float s, float* __restrict__ x, float* __restrict__ px, size_t per_batch_total) {
+                                                        float s, float* __restrict__ x, float* __restrict__ px, size_t per_batch_total, NA... na) {
+    static_assert((!RAG && NOISE == 0) ? sizeof...(NA) == 0 : (NOISE == 0 ? sizeof...(NA) == 1 : sizeof...(NA) == 2), "forms: (), (CfgRows), (CfgRows, NoiseArgs)");
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= per_batch_total) return;
     const int i = *step_idx;
-    const float x0 = s * m[idx] + (1.0f - s) * m[per_batch_total + idx];   // cfg_sampler.py:24-28
-    x[idx] = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], coef[3 * S + i]);
-    if (px) px[idx] = x0;
+    if constexpr (!RAG && NOISE == 0) {
+        const float x0 = s * m[idx] + (1.0f - s) * m[per_batch_total + idx];   // cfg_sampler.py:24-28
+        x[idx] = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], coef[3 * S + i]);
+        if (px) px[idx] = x0;
+    } else {
+        const CfgRows& cr = cfg_rows_of(na...);
+        const int col = (int)(idx % cr.C);
+        const size_t fr = idx / cr.C;
+        int b, t;
+        if constexpr (RAG) {
+            b = cr.rg.row_item[fr];
+            if (b < 0) return;
+            t = cr.rg.row_pos[fr];
+        } else {
+            b = (int)(fr / cr.T);
+            t = (int)(fr % cr.T);
+        }
+        const float x0 = s * m[idx] + (1.0f - s) * m[per_batch_total + idx];
+        if constexpr (NOISE == 0) {
+            x[idx] = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], coef[3 * S + i]);
+        } else {
+            const NoiseArgs& a = cfg_noise_of(na...);
+            float v = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], a.coef_eta[i]);
+            if (i != 0) {                                        // nonzero_mask * sigma * noise
+                const int lp = *a.loop_pos;
+                float z;
+                if constexpr (NOISE == 1) {
+                    const size_t stride = RAG ? (size_t)a.od->noise_stride : per_batch_total;
+                    z = lp < a.od->noise_steps ? a.od->noise[(size_t)lp * stride + idx] : 0.f;       // (the host refuses a run past the buffer)
+                } else if constexpr (RAG) z = step_normal(a.od->item_seed[b], lp, a.od->item_noise_row[b], t, col);
+                else z = step_normal(a.od->seed, lp, b, t, col);
+                v = __builtin_fmaf(a.coef_eta[S + i], z, v);     // (one fixed operation: every instantiation rounds alike)
+            }
+            x[idx] = v;
+        }
+        if (px) px[idx] = x0;
+    }
 }
 
 __global__ __launch_bounds__(256) void cfg4_ddim_kernel(const float* __restrict__ m, const float* __restrict__ coef, int S, const int* __restrict__ step_idx,
@@ -620,6 +667,8 @@ __global__ void set_step_kernel(int* step_idx, int* loop_pos, int s, int l) { *s
 
 // x_start of the loop (gaussian_diffusion.py:1877-1882): the ground path of both persons' roots -- columns 0, 2, 262, 264 -- of both chains is
 // overwritten with x_start[:, :T] before the models run.  x_start [B, xs_T >= T, 524] comes from the call's device-side descriptor.
+// TWO = false: the one-chain form (the stand-alone InterGen sampler: one 524-wide chain, x2 unused).
+template <bool TWO = true>
 __global__ __launch_bounds__(256) void pin_root_kernel(float* __restrict__ x, float* __restrict__ x2, const mmdm_opts_desc* __restrict__ od, int B, int T) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * T * 4) return;
@@ -632,10 +681,11 @@ __global__ __launch_bounds__(256) void pin_root_kernel(float* __restrict__ x, fl
     const float v = xs[((size_t)b * xs_T + t) * NF2 + col];
     const size_t e = (size_t)fr * NF2 + col;
     x[e] = v;
-    x2[e] = v;
+    if constexpr (TWO) x2[e] = v;
 }
 
 // ragged form: one thread per (frame row of the group, pinned column); x_start is packed [sum(lens), 524] like x_T, padding rows are never looked up
+template <bool TWO = true>
 __global__ __launch_bounds__(256) void pin_root_rag_kernel(float* __restrict__ x, float* __restrict__ x2, const mmdm_opts_desc* __restrict__ od, mmdm_rag rg) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= rg.rows * 4) return;
@@ -646,16 +696,18 @@ __global__ __launch_bounds__(256) void pin_root_rag_kernel(float* __restrict__ x
     const size_t e = (size_t)r * NF2 + (k >> 1) * NF + (k & 1) * 2;
     const float v = xs[e];
     x[e] = v;
-    x2[e] = v;
+    if constexpr (TWO) x2[e] = v;
 }
 
 // q_sample at the start of a call (gaussian_diffusion.py:1859-1863, 465-485): x = a * init + b * x_T on both chains (init == nullptr: zeros)
+// TWO = false: one chain of any width (gaussian_diffusion.py:1036-1045)
+template <bool TWO = true>
 __global__ __launch_bounds__(256) void q_sample_kernel(float* __restrict__ x, float* __restrict__ x2, const float* __restrict__ init, float a, float b, size_t total) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const float v = a * (init ? init[idx] : 0.f) + b * x[idx];
     x[idx] = v;
-    x2[idx] = v;
+    if constexpr (TWO) x2[idx] = v;
 }
 
 __global__ void set_opts_kernel(mmdm_opts_desc* d, mmdm_opts_desc v) { *d = v; }
@@ -959,12 +1011,17 @@ extern "C" int mmdm_center_pack_split(const float* motions, int64_t item_stride,
                        total_rows, floor_ws, stream);
 }
 
+// x2 == nullptr: the one-chain forms
 int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rows& r, hipStream_t st) {
     if (r.fr) {
-        hipLaunchKernelGGL(pin_root_rag_kernel, dim3((r.fr->rows * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, *r.fr);
+        const dim3 grid((r.fr->rows * 4 + 255) / 256);
+        if (x2) hipLaunchKernelGGL(pin_root_rag_kernel<true>, grid, dim3(256), 0, st, x, x2, od, *r.fr);
+        else hipLaunchKernelGGL(pin_root_rag_kernel<false>, grid, dim3(256), 0, st, x, x2, od, *r.fr);
         return mmdm_check_launch("pin_root_rag");
     }
-    hipLaunchKernelGGL(pin_root_kernel, dim3((r.n * r.T * 4 + 255) / 256), dim3(256), 0, st, x, x2, od, r.n, r.T);
+    const dim3 grid((r.n * r.T * 4 + 255) / 256);
+    if (x2) hipLaunchKernelGGL(pin_root_kernel<true>, grid, dim3(256), 0, st, x, x2, od, r.n, r.T);
+    else hipLaunchKernelGGL(pin_root_kernel<false>, grid, dim3(256), 0, st, x, x2, od, r.n, r.T);
     return mmdm_check_launch("pin_root");
 }
 
@@ -978,7 +1035,9 @@ int mmdm_set_item_noise(const unsigned long long* seed_host, const int* row_host
 }
 
 int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st) {
-    hipLaunchKernelGGL(q_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, x2, init, a, b, total);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (x2) hipLaunchKernelGGL(q_sample_kernel<true>, grid, dim3(256), 0, st, x, x2, init, a, b, total);
+    else hipLaunchKernelGGL(q_sample_kernel<false>, grid, dim3(256), 0, st, x, x2, init, a, b, total);       // x2 == nullptr: one chain
     return mmdm_check_launch("q_sample");
 }
 
@@ -1000,8 +1059,30 @@ extern "C" int mmdm_cfg_ddim_f32(const float* m, const float* coef, int S, const
     if (B == 0 || T == 0) return MMDM_OK;
     if (!m || !coef || !step_idx || !x || S <= 0 || B < 0 || T < 0 || C <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_cfg_ddim_f32: bad arguments");
     const size_t total = (size_t)B * T * C;
-    hipLaunchKernelGGL(cfg_ddim_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((cfg_ddim_kernel<false, 0>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        m, coef, S, step_idx, cfg_scale, x, pred_xstart, total);
+    return mmdm_check_launch("cfg_ddim");
+}
+
+// The single-chain update with the loop's options (the stand-alone InterGen sampler): form as mmdm_xstart_ddim; r = the B items of the call (ragged: the group
+// of r.fr->rows frame rows, whose uncond half of m follows at the group stride); C = 262 or 524.  Form 0 on uniform rows is mmdm_cfg_ddim_f32's launch.
+int mmdm_cfg_ddim(int form, const float* m, const float* coef, const float* coef_eta, int S, const int* step_idx, const int* loop_pos, const mmdm_opts_desc* od,
+                  float cfg_scale, float* x, float* pred_xstart, const mmdm_rows& r, int C, hipStream_t st) {
+    if (form < 0 || form > 2) return mmdm_set_error(MMDM_ERR_ARG, "cfg_ddim: form %d", form);
+    const size_t total = (r.fr ? (size_t)r.fr->rows : (size_t)r.n * r.T) * C;
+    if (total == 0) return MMDM_OK;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    const NoiseArgs na{coef_eta, od, loop_pos};
+    const CfgRows cr{r.T, C, r.fr ? *r.fr : mmdm_rag{}};
+    if (r.fr) {
+        if (form == 0) hipLaunchKernelGGL((cfg_ddim_kernel<true, 0, CfgRows>), grid, block, 0, st, m, coef, S, step_idx, cfg_scale, x, pred_xstart, total, cr);
+        else if (form == 1) hipLaunchKernelGGL((cfg_ddim_kernel<true, 1, CfgRows, NoiseArgs>), grid, block, 0, st, m, coef, S, step_idx, cfg_scale, x, pred_xstart, total, cr, na);
+        else hipLaunchKernelGGL((cfg_ddim_kernel<true, 2, CfgRows, NoiseArgs>), grid, block, 0, st, m, coef, S, step_idx, cfg_scale, x, pred_xstart, total, cr, na);
+        return mmdm_check_launch("cfg_ddim_rag");
+    }
+    if (form == 0) hipLaunchKernelGGL((cfg_ddim_kernel<false, 0>), grid, block, 0, st, m, coef, S, step_idx, cfg_scale, x, pred_xstart, total);
+    else if (form == 1) hipLaunchKernelGGL((cfg_ddim_kernel<false, 1, CfgRows, NoiseArgs>), grid, block, 0, st, m, coef, S, step_idx, cfg_scale, x, pred_xstart, total, cr, na);
+    else hipLaunchKernelGGL((cfg_ddim_kernel<false, 2, CfgRows, NoiseArgs>), grid, block, 0, st, m, coef, S, step_idx, cfg_scale, x, pred_xstart, total, cr, na);
     return mmdm_check_launch("cfg_ddim");
 }
 

@@ -143,6 +143,10 @@ int mmdm_blend_cfg(const float* out1, const float* out2, const float* w, int mod
 int mmdm_xstart_ddim(int form, const float* model_out, const float* stats, const float* coef, const float* coef_eta, int S, const int* step_idx,
                      const int* loop_pos, const mmdm_opts_desc* od, float* x, float* x2, float* pred_xstart, float* pred_xstart2, float* floor_ws,
                      const mmdm_rows& r, int align, hipStream_t st);
+// The single-chain update (2-way CFG combine + DDIM) with the same forms, on one chain of width C = 262 or 524; form 0 on uniform rows is mmdm_cfg_ddim_f32's kernel
+int mmdm_cfg_ddim(int form, const float* m, const float* coef, const float* coef_eta, int S, const int* step_idx, const int* loop_pos, const mmdm_opts_desc* od,
+                  float cfg_scale, float* x, float* pred_xstart, const mmdm_rows& r, int C, hipStream_t st);
+// x2 == nullptr in the next two: the one-chain forms
 int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rows& r, hipStream_t st);
 int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st);
 int mmdm_hist_copy(const float* src, const mmdm_hist_desc* hd, int which, size_t count, const int* loop_pos, hipStream_t st);

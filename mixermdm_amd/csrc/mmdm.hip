@@ -344,6 +344,9 @@ struct mmdm_handle_s {
 
 namespace {
 
+// which denoisers a sampler mode holds: 2 and 4 run denoiser 2 alone, 1 runs denoiser 1 alone
+bool has_d1_of(int single_only) { return single_only != 2 && single_only != 4; }
+
 int herr(mmdm_handle h, int code) {
     if (code) snprintf(h->err, sizeof(h->err), "%s", g_err);
     return code;
@@ -825,14 +828,17 @@ int repack(const Ctx& c, const ModuleW& m, const float* x, int ldx, float* xp, i
 
 // denoiser1 on the CFG-doubled batch n; xa [B or n rows...]: source rows are taken from `x` with `xrows` samples, repeated to n.
 // Sequence order in h: person-major: seq = p*n + b.
+// one_emb: `ss` holds ONE row group [n] that conditions every norm of both persons (InterDenoiser's single emb, intergen.py:266-270) instead of the three
+// groups [emb_1 | emb_2 | emb_interaction].
 int run_denoiser(const Ctx& c, const ModuleW& m, bool interaction, const float* x, int xb, int npers, int ldx, int n, int T,
-                 const float* ss, int ss_ld, float* out, int ldo) {
+                 const float* ss, int ss_ld, float* out, int ldo, bool one_emb = false) {
     const int D = m.st.D;
     StackRun r;
     r.nseq = npers * n; r.T = T; r.ss = ss; r.ss_ld = ss_ld;
     r.sa_row0 = 0; r.sa_rows = npers * n;
     r.ffn_row0 = 0; r.ffn_rows = npers * n;
     r.ca_row0 = 2 * n; r.ca_rows = n;
+    if (one_emb) { r.sa_rows = r.ffn_rows = n; r.ca_row0 = 0; }
     r.ca_mode = interaction ? 1 : 0;
     r.kv_src = nullptr;
     // embed: `x` holds xb samples (xb == n, or xb == n/2 when cond/uncond halves share the same x: cfg_sampler.py:41-42)
@@ -1040,7 +1046,14 @@ int run_step(const Ctx& c) {
     const int B = H->B, T = H->T, n = 2 * B;
     // the single-chain samplers run ONE stream of kernels: split the GEMMs' fractional last round (gemm_f32.hip; results are bit-identical);
     // scoped: the calling thread's stateless mmdm_linear_f32 calls keep the default rule afterwards
-    TailScope tail_scope((H->cfg.single_only == 1 || H->cfg.single_only == 2) ? 10 : 0);
+    TailScope tail_scope((H->cfg.single_only == 1 || H->cfg.single_only == 2 || H->cfg.single_only == 4) ? 10 : 0);
+    if (H->cfg.single_only == 4) {   // stand-alone InterDenoiser under the 2-way CFG (intergen.py:20-213, cfg_sampler.py:12-28): one chain [B, T, 524], one emb per CFG row
+        if (H->pinned) RC(mmdm_pin_root(H->x, nullptr, H->d_opts, c.rows(B, T), c.st));
+        RC(cond_vectors(c, H->d2, H->txt_d2, H->se_d2, H->ss_d2, n));
+        RC(run_denoiser(c, H->d2, true, H->x, B, 2, NF2, n, T, H->ss_d2, ss_ld_of(H->d2), H->o2, NF2, true));
+        RC(mmdm_cfg_ddim(H->noise_form, H->o2, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts, H->cfg.cfg_scale, H->x, H->px1, c.rows(B, T), NF2, c.st));
+        return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
+    }
     if (H->cfg.single_only == 1) {
         if (H->d1.kind == 1) {
             RC(run_denoiser_mdm(c, H->d1, H->x, B, 1, NF, n, T, H->cond_cat, H->td1, H->o1, NF));
@@ -1201,8 +1214,10 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     if (!cfg || !out) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: null argument");
     if (cfg->nfeats != NF) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_create: nfeats must be 262");
     const int so = cfg->single_only;
-    if (so < 0 || so > 3) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: single_only must be 0, 1, 2 or 3");
-    const bool has_d1 = so != 2, has_d2 = so != 1, has_mx = so == 0, two_models = so == 0 || so == 3;
+    if (so < 0 || so > 4) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: single_only must be 0, 1, 2, 3 or 4");
+    if (so == 4 && cfg->model2_kind != 1)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: single_only = 4 is the stand-alone InterGen sampler and needs model2_kind = 1 (InterDenoiser), got model2_kind = %d", cfg->model2_kind);
+    const bool has_d1 = has_d1_of(so), has_d2 = so != 1, has_mx = so == 0, two_models = so == 0 || so == 3;
     if (cfg->model1_kind < 0 || cfg->model1_kind > 1) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: model1_kind must be 0 (in2IN individual) or 1 (MDM)");
     const bool mdm = has_d1 && cfg->model1_kind == 1;
     if (mdm && so == 3) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: the dual sampler composes two in2IN denoisers (model1_kind must be 0)");
@@ -1243,7 +1258,7 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     const int B = c.max_batch, T = c.max_frames, n = (so == 2 ? 4 : 2) * B, td = c.text_dim;
     const int Dm = has_mx ? c.m_latent : 4, Fm = has_mx ? c.m_ff : 4;
     h->td1 = mdm ? D1 : td;                                  // MDMDenoiser adds its cond slice to the timestep embedding: latent-sized (mdm.py:279)
-    h->cond_w = so == 0 ? 6 * td + 2 * h->td1 : so == 1 ? h->td1 : so == 2 ? 3 * td : 5 * td;
+    h->cond_w = so == 0 ? 6 * td + 2 * h->td1 : so == 1 ? h->td1 : so == 2 ? 3 * td : so == 4 ? td : 5 * td;
     if (parent) {
         // borrow the parent's weights: the module descriptors are tables of pointers into the shared weight block (incl. the low-precision
         // twins and their layout flags as mmdm_prepare left them); everything that depends on a call or a schedule is this handle's own
@@ -1356,7 +1371,7 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     }
     if (const char* e = getenv("MMDM_GRAPH_CACHE")) { long v = atol(e); if (v >= 1 && v <= 64) h->graph_cap = (size_t)v; }
     // ragged calls (mmdm_begin_ragged): row maps for up to 4 groups of max_batch * max_frames rows, and per module the PE rows of a group
-    if (so <= 1) {
+    if (so <= 1 || so == 4) {
         const size_t cap = (size_t)B * T, nb = (size_t)(B < MMDM_RAG_MAX_ITEMS ? B : MMDM_RAG_MAX_ITEMS), G = 4;
         if ((rc = dalloc(h, &tmp, 3 * nb + 2 * cap + G * cap + 2 * G * nb))) return fail(rc);
         h->d_rag = reinterpret_cast<int*>(tmp);
@@ -1372,7 +1387,7 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
             h->d_tok_item_off = h->d_tok; h->d_tok_item_len = h->d_tok_item_off + nb; h->d_tok_row_item = h->d_tok_item_len + nb;
             h->d_tok_row_pos = h->d_tok_row_item + tcap; h->d_tok_seq_off = h->d_tok_row_pos + tcap; h->d_tok_seq_len = h->d_tok_seq_off + G * nb;
         }
-        if (so == 0) {      // per-item generator identity (8-byte seeds first: the allocation's own alignment serves them)
+        if (so == 0 || so == 4) {      // per-item generator identity (8-byte seeds first: the allocation's own alignment serves them)
             if ((rc = dalloc(h, &tmp, 3 * (size_t)MMDM_RAG_MAX_ITEMS))) return fail(rc);
             h->d_item_seed = reinterpret_cast<unsigned long long*>(tmp);
             h->d_item_noise_row = reinterpret_cast<int*>(h->d_item_seed + MMDM_RAG_MAX_ITEMS);
@@ -1586,7 +1601,7 @@ extern "C" int mmdm_set_schedule(mmdm_handle h, const int* timestep_map, const f
     // cached step graphs stay valid: S is part of their key, the tables are device data at fixed addresses
     Ctx c{h, st, &h->sa};
     ProfPause pause(h->prof);
-    int rc = h->cfg.single_only != 2 ? build_time_tab(c, h->d1) : MMDM_OK;
+    int rc = has_d1_of(h->cfg.single_only) ? build_time_tab(c, h->d1) : MMDM_OK;
     if (!rc && h->cfg.single_only != 1) rc = build_time_tab(c, h->d2);
     if (!rc && h->cfg.single_only == 0) rc = build_time_tab(c, h->mx);
     h->begun = false;
@@ -1604,7 +1619,7 @@ extern "C" int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S) 
 
 extern "C" int mmdm_set_eta(mmdm_handle h, const float* coef_eta_host, int S) {
     if (!h) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_eta: null handle");
-    if (h->cfg.single_only != 0)
+    if (h->cfg.single_only != 0 && h->cfg.single_only != 4)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_eta: eta > 0 covers the two-chain MixerMDM sampler (single_only = %d)", h->cfg.single_only));
     if (h->S == 0) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_set_eta: call mmdm_set_schedule first"));
     if (!coef_eta_host) { h->eta_set = false; h->begun = false; return MMDM_OK; }
@@ -1630,7 +1645,7 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     const bool any = o->noise_source || o->noise || o->x_start || o->init_image || o->init_zeros || o->skip_timesteps;
     if (lens && h->eta_set && !ro)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: eta is set on the handle; the stochastic update covers uniform batches and ragged calls that name a noise source (mmdm_begin_ragged_opts); or clear it with mmdm_set_eta(h, NULL, 0)"));
-    if (any && h->cfg.single_only != 0)
+    if (any && h->cfg.single_only != 0 && h->cfg.single_only != 4)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "%s: step noise, x_start, init_image and skip_timesteps cover the two-chain MixerMDM sampler (single_only = %d)", who, h->cfg.single_only));
     if (o->noise_source < 0 || o->noise_source > 2 || (o->noise_source == 1 && !o->noise))
         return herr(h, mmdm_set_error(MMDM_ERR_ARG, "%s: noise_source must be 0 (none), 1 (buffer, not NULL) or 2 (seed)", who));
@@ -1650,9 +1665,9 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     if (lens && h->mask_rows)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: a key mask is set on the handle; ragged batches carry their lengths instead (clear it with mmdm_set_key_mask(h, NULL, 0, 0))"));
     if (lens) {
-        if (h->cfg.single_only > 1 || !h->d_rag || (h->d1.kind == 1 && !h->d_tok))
+        if ((h->cfg.single_only > 1 && h->cfg.single_only != 4) || !h->d_rag || (h->d1.kind == 1 && !h->d_tok))
             return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: ragged batches cover the two-chain MixerMDM sampler and the single-person sampler over in2IN / InterGen / MDM denoisers"));
-        const StackW* sts[3] = {h->cfg.single_only != 2 ? &h->d1.st : nullptr, h->cfg.single_only != 1 ? &h->d2.st : nullptr, h->cfg.single_only == 0 ? &h->mx.st : nullptr};
+        const StackW* sts[3] = {has_d1_of(h->cfg.single_only) ? &h->d1.st : nullptr, h->cfg.single_only != 1 ? &h->d2.st : nullptr, h->cfg.single_only == 0 ? &h->mx.st : nullptr};
         for (const StackW* w : sts)
             if (w && w->D / w->H != 64 && w->D / w->H != 128)
                 return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: head size %d (the ragged attention kernels cover 64 and 128)", w->D / w->H));
@@ -1714,7 +1729,13 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     if (h->cfg.single_only == 3 && !h->dual_w_set) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_begin: call mmdm_set_dual_weights after mmdm_set_schedule"));
     ProfPause pause(h->prof);
     int rc = MMDM_OK;
-    if (h->cfg.single_only == 2) {
+    if (h->cfg.single_only == 4) {
+        // cond [B, td], CFG-doubled with a zero uncond half (cfg_sampler.py:19-23); InterDenoiser has ONE emb (intergen.py:266): one text embedding per CFG row
+        HIPCHK(hipMemsetAsync(h->cond_cat, 0, (size_t)n * td * sizeof(float), st));
+        HIPCHK(hipMemcpyAsync(h->cond_cat, cond, (size_t)B * td * sizeof(float), hipMemcpyDeviceToDevice, st));
+        rc = text_rows(c, h->d2, h->cond_cat, td, 0, h->txt_d2, 0, n);
+        RC(load_x(h->x, NF2));
+    } else if (h->cfg.single_only == 2) {
         // 4 CFG copies of cond [B, 3*td]: full | interaction only (first td columns) | individuals only (columns td..) | zeros
         const int n4 = 4 * B, ldc = 3 * td;
         HIPCHK(hipMemsetAsync(h->cond_cat, 0, (size_t)n4 * ldc * sizeof(float), st));
@@ -1951,7 +1972,7 @@ extern "C" int mmdm_module_forward(mmdm_handle h, int which, const float* x, con
     } else if (n <= 0 || (n & 1) || n / 2 > h->cfg.max_batch * (so_ == 2 ? 2 : 1) || T <= 0 || T > h->cfg.max_frames)
         return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_module_forward: n=%d (even, <= 2*max_batch) T=%d out of range", n, T));
     if (t < 0 || t >= 5000) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_module_forward: timestep %d out of range", t));
-    if (which < 0 || which > 4 || (so_ == 1 && which != 0) || (so_ == 2 && which != 1) || (so_ == 3 && (which == 2 || which == 0)) || (so_ != 3 && which == 3)) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_module_forward: bad module %d", which));
+    if (which < 0 || which > 4 || (so_ == 1 && which != 0) || ((so_ == 2 || so_ == 4) && which != 1) || (so_ == 3 && (which == 2 || which == 0)) || (so_ != 3 && which == 3)) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_module_forward: bad module %d", which));
     hipStream_t st = static_cast<hipStream_t>(stream);
     Ctx c{h, st, &h->sa};
     if (h->mask_rows && which == 3) return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_module_forward: module 3 (dual_individual) takes no key mask"));
@@ -1959,12 +1980,12 @@ extern "C" int mmdm_module_forward(mmdm_handle h, int which, const float* x, con
     h->call_stream = st;                    // mmdm_set_key_mask waits for this stream before it replaces the mask      // which 0, 1, 2: the caller's (doubled) n rows; which 4: B rows, repeated by the % of the kernels
     const int td = h->cfg.text_dim;
     ProfPause pause(h->prof);
-    TailScope tail_scope((so_ == 1 || so_ == 2) ? 10 : 0);
+    TailScope tail_scope((so_ == 1 || so_ == 2 || so_ == 4) ? 10 : 0);
     // The forward borrows slot 0 of the schedule tables (timestep_map[0] and row 0 of every time_tab) for a one-entry schedule
     // time_tab[0] = time_embed(pe[t]) and puts the caller's entries back afterwards, so a schedule set before survives the call
     // (a sampling call in progress does not: text embeddings, scratch and the step index are overwritten -- mmdm_begin again).
     const int S_keep = h->S;
-    ModuleW* mods[3] = {so_ != 2 ? &h->d1 : nullptr, so_ != 1 ? &h->d2 : nullptr, so_ == 0 ? &h->mx : nullptr};
+    ModuleW* mods[3] = {has_d1_of(so_) ? &h->d1 : nullptr, so_ != 1 ? &h->d2 : nullptr, so_ == 0 ? &h->mx : nullptr};
     const size_t Dst = max2(max2(h->d1.st.D, h->d2.st.D), h->mx.st.D);
     if (S_keep > 0)
         for (int k = 0; k < 3; ++k)
@@ -2062,6 +2083,8 @@ extern "C" int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host,
     if (!valid_host) { h->mask_rows = 0; h->mask_T = 0; return MMDM_OK; }
     if (h->cfg.precision != 0 && h->cfg.precision != 2)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: precision %d handle -- the bf16 attention forms take no key mask (precision 0 and 2 only)", h->cfg.precision));
+    if (h->cfg.single_only == 4)
+        return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: single_only = 4 -- the stand-alone InterGen sampler takes no key mask (ragged batches carry the lengths: mmdm_begin_ragged)"));
     if (h->cfg.single_only != 2 && h->d1.kind == 1)
         return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_set_key_mask: model1_kind = 1 -- the MDM encoder's src_key_padding_mask is not implemented"));
     if (h->cfg.single_only >= 2)

@@ -838,3 +838,406 @@ class in2IN(nn.Module):
             batch = self.text_process(batch, "individual", out_name="cond_individual_individual1")
         batch.update(self.decode_motion(batch))
         return batch
+
+
+# ---- stand-alone InterGen and MDM samplers ---------------------------------------------------------------------------------------
+def _unwrap_checkpoint(state_dict):
+    """A raw state dict, or a Lightning checkpoint {"state_dict": {"model.<key>": ...}} (mixermdm.py:43-59): the ``model.`` prefix is dropped."""
+    sd = state_dict["state_dict"] if "state_dict" in state_dict and isinstance(state_dict["state_dict"], dict) else state_dict
+    if sd and all(k.startswith("model.") for k in sd):
+        sd = {k[len("model."):]: v for k, v in sd.items()}
+    return dict(sd)
+
+
+def _unsupported(fn, *a, **k):
+    """Runs a sampler call; a refusal of the library (MMDM_ERR_UNSUPPORTED) becomes NotImplementedError with the library's message."""
+    from ._lib import MMDMError
+    try:
+        return fn(*a, **k)
+    except MMDMError as e:
+        if e.status == _KeyMask.UNSUPPORTED:
+            raise NotImplementedError(str(e)) from None
+        raise
+
+
+def _loop_forms(batches, eta, who):
+    """MixerMDM.sample_many's rules for the loop arguments a batch dict may carry: 'x_start' / 'init_image' for every batch or for none; at eta > 0
+    ONE noise form per call -- 'seed' (an un-named one is drawn from torch's default generator, in batch order) or 'step_noise'.
+    -> (form "seed" | "noise" | None, seeds per batch)."""
+    has = lambda k: [b.get(k) is not None for b in batches]
+    for k in ("x_start", "init_image"):
+        if any(has(k)) and not all(has(k)):
+            raise ValueError(f"{who}: batch {has(k).index(not has(k)[0])} differs from batch 0 in whether it gives {k!r}: give it for every batch or for none")
+    form, seeds = None, [None] * len(batches)
+    if eta:
+        for i, b in enumerate(batches):
+            sd, sn = b.get("seed"), b.get("step_noise")
+            if sd is not None and sn is not None:
+                raise ValueError(f"{who}: batch {i} gives both 'seed' and 'step_noise'")
+            f = "noise" if sn is not None else "seed"
+            if form is not None and f != form:
+                raise ValueError(f"{who}: batch {i} names its step noise as a {f!r}, batch 0 as a {form!r}: one noise form per call")
+            form = f
+            if f == "seed":
+                seeds[i] = int(sd) if sd is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+    return form, seeds
+
+
+class _StandaloneDiffusion(nn.Module):
+    """What InterDiffusion and MDM share: parameters under the reference's names, one Sampler handle, the schedule, ragged batching of many calls."""
+    WIDTH = 524
+
+    def _apply(self, fn, recurse=True):
+        self._dirty = True
+        return super()._apply(fn, recurse)
+
+    @property
+    def device(self):
+        return next(self.parameters()).device
+
+    def load_state_dict(self, state_dict, strict=True):
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("sequence_pos_encoder.pe")}
+        self._dirty = True
+        return super().load_state_dict(sd, strict=strict)
+
+    def _get_sampler(self, B, T):
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs on an MI355X only: call .to('cuda:N') first (no CPU path)")
+        s = self._sampler
+        if s is None or B > s.cfg.max_batch or T > s.cfg.max_frames or s.device != dev or s._precision != self.precision:
+            if s is not None:
+                s.close()
+            s = self._make_sampler(max(B, s.cfg.max_batch if s is not None and s._precision == self.precision else 1), max(T, self.num_frames), dev)
+            s._precision = self.precision
+            self._sampler, self._dirty = s, True
+        if self._dirty:
+            s.load_state_dict(self._sampler_state())
+            s.prepare()
+            s._strategy = None
+            self._dirty = False
+        if s._strategy != self.sampling_strategy:
+            s.set_schedule(self.sampling_strategy, self.beta_scheduler, self.diffusion_steps)
+            s._strategy = self.sampling_strategy
+        return s
+
+    def _inputs(self, batch):
+        cond = batch["cond"]
+        B, T = cond.shape[0], int(batch["motion_lens"][0])
+        x_T = batch["x_T"] if batch.get("x_T") is not None else torch.randn(B, T, self.WIDTH, device=self.device)
+        if tuple(x_T.shape) != (B, T, self.WIDTH):
+            raise ValueError(f"{type(self).__name__}: x_T [{B}, {T}, {self.WIDTH}] expected, got {tuple(x_T.shape)}")
+        return cond, x_T, B, T
+
+    def _sample_many(self, batches, batching, max_rows, max_items, eta=0.0, skip_timesteps=0, options=True):
+        who = f"{type(self).__name__}.sample_many"
+        if batching not in ("sequential", "ragged"):
+            raise ValueError(f'{who}: batching {batching!r} not recognized ("ragged" or "sequential")')
+        eta, skip = float(eta), int(skip_timesteps)
+        if eta < 0:
+            raise ValueError(f"eta={eta} must be >= 0")
+        form, seeds = _loop_forms(batches, eta, who)
+        has = lambda k: any(b.get(k) is not None for b in batches)
+        use_opts = bool(eta or skip or has("x_start") or has("init_image"))
+        if use_opts and not options:
+            # the library decides: its refusal (mode 1 keeps the option refusals) comes back as NotImplementedError with its message
+            cond, x_T, B, T = self._inputs(batches[0])
+            _unsupported(self._get_sampler(B, T).sample, cond, x_T, eta=eta, skip_timesteps=skip, seed=seeds[0], x_start=batches[0].get("x_start"),
+                         init_image=batches[0].get("init_image"))
+            raise NotImplementedError(f"{who}: the loop options are not covered by this sampler")
+        if batching == "sequential":
+            out = []
+            for i, b in enumerate(batches):
+                kw = dict(eta=eta, skip_timesteps=skip, seed=seeds[i], step_noise=b.get("step_noise") if form == "noise" else None,
+                          x_start=b.get("x_start"), init_image=b.get("init_image")) if use_opts else {}
+                out.append({"output": self.forward(b, **kw)["output"]})
+            return out
+        ins = [self._inputs(b) for b in batches]
+        Bs, Ts = [v[2] for v in ins], [v[3] for v in ins]
+        motions = [(i, j) for i, nb in enumerate(Bs) for j in range(nb)]
+        groups, cur, rows = [], [], 0
+        for (i, j) in motions:
+            if cur and (rows + Ts[i] > max_rows or len(cur) >= max_items):
+                groups.append(cur)
+                cur, rows = [], 0
+            cur.append((i, j))
+            rows += Ts[i]
+        if cur:
+            groups.append(cur)
+        Tm = max(max(Ts), self.num_frames)
+        smp = self._get_sampler(max(max(len(g) for g in groups), -(-max(sum(Ts[i] for i, _ in g) for g in groups) // Tm)), Tm)
+        S = smp.schedule.num_timesteps
+        if not 0 <= skip < S:
+            raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
+        steps = S - skip
+        if form == "noise":
+            for i, b in enumerate(batches):
+                sn = b["step_noise"]
+                if sn.dim() != 4 or sn.shape[0] < steps or tuple(sn.shape[1:]) != (Bs[i], Ts[i], self.WIDTH):
+                    raise ValueError(f"{who}: batch {i}: step_noise [>= {steps}, {Bs[i]}, {Ts[i]}, {self.WIDTH}] expected, got {tuple(sn.shape)}")
+        for k in ("x_start", "init_image"):
+            for i, b in enumerate(batches):
+                if b.get(k) is not None and (b[k].dim() != 3 or b[k].shape[0] != Bs[i]):
+                    raise ValueError(f"{who}: batch {i}: {k} [{Bs[i]}, T, {self.WIDTH}] expected, got {tuple(b[k].shape)}")
+        outs = [[None] * nb for nb in Bs]
+        pend = []
+        if eta:
+            smp.set_eta(eta)
+        try:
+            for g in groups:
+                kw = {}
+                if use_opts:
+                    kw["skip_timesteps"] = skip
+                    if form == "seed":
+                        kw["seeds"], kw["noise_rows"] = [seeds[i] for i, _ in g], [j for _, j in g]
+                    elif form == "noise":
+                        kw["noise"] = [batches[i]["step_noise"][:steps, j] for i, j in g]
+                    for k in ("x_start", "init_image"):
+                        if batches[g[0][0]].get(k) is not None:
+                            kw[k] = [batches[i][k][j] for i, j in g]
+                items, _, ev = smp.sample_ragged_async(torch.cat([ins[i][0][j:j + 1] for i, j in g], 0), [ins[i][1][j] for i, j in g], [Ts[i] for i, _ in g], **kw)
+                pend.append((g, items, ev))
+        finally:
+            if eta:
+                smp.set_eta(0.0)
+        for g, items, ev in pend:
+            ev.synchronize()
+            for (i, j), it in zip(g, items):
+                outs[i][j] = it
+        torch.cuda.current_stream(self.device).wait_stream(smp.stream)
+        return [{"output": torch.stack(o, 0)} for o in outs]
+
+
+class InterDiffusion(_StandaloneDiffusion):
+    """InterDiffusion (src/models/intergen.py:96-213): InterDenoiser ``net`` under ClassifierFreeSampleModel(cfg.CFG_WEIGHT) in the single-chain DDIM loop,
+    [B, T, 524] in the model's normalised space.  Runs on ``Sampler(single_only=4, model2_kind=1)``; ``.precision`` picks the handle's mode (all four).
+    ``forward`` also takes the loop's other arguments (GaussianDiffusion.ddim_sample_loop, gaussian_diffusion.py:946-1069), which the reference's call site
+    leaves at their defaults (x_start=None, intergen.py:203-212)."""
+    WIDTH = 524
+
+    def __init__(self, cfg, sampling_strategy="ddim50"):
+        super().__init__()
+        self.cfg = cfg
+        self.nfeats = cfg.INPUT_DIM
+        self.latent_dim, self.ff_size, self.num_layers, self.num_heads = cfg.LATENT_DIM, cfg.FF_SIZE, cfg.NUM_LAYERS, cfg.NUM_HEADS
+        self.cfg_weight = cfg.CFG_WEIGHT
+        self.diffusion_steps, self.beta_scheduler = cfg.DIFFUSION_STEPS, cfg.BETA_SCHEDULER
+        self.sampling_strategy = sampling_strategy
+        self.text_dim = 768
+        self.num_frames = 300
+        self.precision = "fp32"
+        if self.nfeats != 262:
+            raise NotImplementedError(f"INPUT_DIM={self.nfeats}: the HIP path is built for 262 pose features per person")
+        self.betas = get_named_beta_schedule(self.beta_scheduler, self.diffusion_steps)
+        from .synthetic import denoiser_shapes
+        for k, shp in denoiser_shapes("net.", self.latent_dim, self.ff_size, self.num_layers).items():
+            _holder_tree(self, k, torch.zeros(shp))
+        self._sampler, self._dirty = None, True
+
+    def _make_sampler(self, B, T, dev):
+        return Sampler(d_latent=self.latent_dim, d_ff=self.ff_size, d_layers=self.num_layers, d_heads=self.num_heads, single_only=4, model2_kind=1,
+                       cfg_scale=self.cfg_weight, max_batch=B, max_frames=T, device=dev, precision=self.precision)
+
+    def _sampler_state(self):
+        return {"denoiser2." + k[len("net."):]: p.data for k, p in self.named_parameters()}
+
+    def forward(self, batch, *, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0):
+        """intergen.py:184-213 -> {"output": [B, T, 524]}.  eta > 0 needs its step noise: step_noise [>= S - skip, B, T, 524] or seed (the device generator;
+        with neither, a seed is drawn from torch's default generator)."""
+        cond, x_T, B, T = self._inputs(batch)
+        eta = float(eta)
+        if eta < 0:
+            raise ValueError(f"eta={eta} must be >= 0")
+        if step_noise is not None and seed is not None:
+            raise ValueError("give the step noise as a buffer (step_noise=) or as a seed (seed=), not both")
+        if eta == 0.0:
+            step_noise = seed = None
+        elif step_noise is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        s = self._get_sampler(B, T)
+        S, skip = s.schedule.num_timesteps, int(skip_timesteps)
+        if not 0 <= skip < S:
+            raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
+        try:
+            out = s.sample(cond, x_T, eta=eta, noise=step_noise[:S - skip] if step_noise is not None else None, seed=seed, x_start=x_start,
+                           init_image=init_image, skip_timesteps=skip)
+        finally:
+            if eta:                                  # eta belongs to this call
+                s.set_eta(0.0)
+        return {"output": out}
+
+    def sample_many(self, batches, batching="ragged", max_rows=4800, max_items=64, *, eta=0.0, skip_timesteps=0):
+        """Many forward calls at once (batch dicts with 'cond' [b, 768], 'motion_lens', optionally 'x_T' [b, T, 524]) -> one {"output"} per batch, every
+        motion BIT-IDENTICAL to that batch's own forward call on the same x_T and options.  "sequential" = one call after the other; "ragged" = the motions
+        packed into ragged batches of <= max_rows frames / <= max_items motions.  eta / skip_timesteps belong to the call; 'seed' / 'step_noise' /
+        'x_start' / 'init_image' in the batch dicts follow MixerMDM.sample_many's rules."""
+        return self._sample_many(batches, batching, max_rows, max_items, eta, skip_timesteps)
+
+
+class InterGen(nn.Module):
+    """InterGen(cfg) facade (src/models/intergen.py:20-94) around InterDiffusion.  Checkpoint keys: ``decoder.net.*`` (the denoiser), the aliased CLIP tower
+    ``token_embedding.* / positional_embedding / clip_transformer.* / ln_final.*`` and the text head ``clipTransEncoder.* / clip_ln.*``; a Lightning
+    checkpoint {"state_dict": {"model.<key>": ...}} is unwrapped.  Text: when the checkpoint carries tower and head, ``text_process`` runs them on the GPU
+    (mixermdm_amd.text); otherwise put the encoded 'cond' [B, 768] in the batch or set ``text_encoder(batch, mode, text_name, out_name)``."""
+    TEXT_PREFIXES = ("token_embedding.", "positional_embedding", "clip_transformer.", "ln_final.", "clipTransEncoder.", "clip_ln.")
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        self.latent_dim = cfg.LATENT_DIM
+        self.decoder = InterDiffusion(cfg, sampling_strategy=cfg.STRATEGY)
+        self.text_encoder = None
+        self.text_num_heads = 8               # nhead of the clipTransEncoder layers (intergen.py:41)
+        self._text_sd, self._text = None, None
+
+    @property
+    def device(self):
+        return self.decoder.device
+
+    def load_state_dict(self, state_dict, strict=True):
+        sd = _unwrap_checkpoint(state_dict)
+        unexpected = [k for k in sd if not k.startswith("decoder.") and not k.startswith(self.TEXT_PREFIXES)]
+        if strict and unexpected:
+            raise RuntimeError("Error(s) in loading state_dict for InterGen:\n\tUnexpected key(s): %s" % unexpected[:8])
+        res = self.decoder.load_state_dict({k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}, strict=strict)
+        txt = {k: v for k, v in sd.items() if k.startswith(self.TEXT_PREFIXES)}
+        if "token_embedding.weight" in txt and "clip_ln.weight" in txt:
+            self._text_sd, self._text = txt, None
+        return res
+
+    def text_process(self, batch, mode="interaction", text_name="text", out_name="cond"):
+        if out_name in batch:
+            return batch
+        if mode not in ("individual", "interaction"):
+            raise ValueError("Mode not recognized")
+        if self.text_encoder is not None:
+            return self.text_encoder(batch, mode, text_name, out_name)
+        if self._text_sd is None:
+            raise NotImplementedError("text encoding (CLIP tower + clipTransEncoder, intergen.py:68-94) is upstream of the HIP path: "
+                                      f"put the encoded '{out_name}' in the batch, load a checkpoint that carries the text modules, or set model.text_encoder")
+        from .text import ClipTextTower, TextHead, tokenize
+        dev = self.device
+        if self._text is None or self._text[0].table.device != dev:
+            sd = self._text_sd
+            heads = sd["clip_transformer.resblocks.0.attn.in_proj_weight"].shape[1] // 64 if "clip_transformer.resblocks.0.attn.in_proj_weight" in sd else 12
+            self._text = (ClipTextTower(sd, "", heads, dev), TextHead(sd, "clipTransEncoder.", "clip_ln", self.text_num_heads, dev))
+        tower, head = self._text
+        tok = torch.as_tensor(batch["tokens_" + text_name]) if "tokens_" + text_name in batch else tokenize(batch[text_name])
+        batch[out_name] = head(tower(tok), tok)
+        return batch
+
+    def decode_motion(self, batch):
+        batch.update(self.decoder(batch))
+        return batch
+
+    def forward_test(self, batch):
+        """intergen.py:63-66: the batch, with 'cond' and 'output' [B, T, 524] (normalised space) added."""
+        batch = self.text_process(batch)
+        batch.update(self.decode_motion(batch))
+        return batch
+
+    def forward(self, batch, **loop_kw):
+        """Sampling with the loop's other arguments (InterDiffusion.forward's keywords)."""
+        batch = self.text_process(batch)
+        batch.update(self.decoder(batch, **loop_kw))
+        return batch
+
+    def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
+        """InterDiffusion.sample_many after text_process; mode / inflight / keep_history are accepted for generate_for_evaluation's call and unused (one chain,
+        no history side outputs)."""
+        with torch.no_grad():
+            batches = [self.text_process(dict(b)) for b in batches]
+        return self.decoder.sample_many(batches, batching=batching, max_rows=max_rows, max_items=max_items, eta=eta, skip_timesteps=skip_timesteps)
+
+
+class MDM(_StandaloneDiffusion):
+    """MDM(cfg, num_frames, sampling_strategy) (src/models/mdm.py:9-66, 195-231): MDMDenoiser ``model`` under ClassifierFreeSampleModel(cfg.CFG_WEIGHT),
+    one person, [B, T, 262]; runs on ``Sampler(single_only=1, model1_kind=1)`` -- precision "fp32" or "fp32_split", as the handle allows.  Parameters:
+    ``model.*`` and ``embed_text.*``; text goes through MDM's own CLIP model + embed_text (mixermdm_amd.text.MdmTextHead) when the checkpoint carries
+    ``clip_model.*``, else pass 'cond' [B, LATENT_DIM] (what embed_text hands the denoiser).  The loop options are refused by the library for this mode:
+    NotImplementedError with its message."""
+    WIDTH = 262
+
+    def __init__(self, cfg, num_frames=300, sampling_strategy="ddim50"):
+        super().__init__()
+        self.cfg = cfg
+        self.nfeats = cfg.INPUT_DIM
+        self.latent_dim, self.ff_size, self.num_layers, self.num_heads = cfg.LATENT_DIM, cfg.FF_SIZE, cfg.NUM_LAYERS, cfg.NUM_HEADS
+        self.cfg_weight = cfg.CFG_WEIGHT
+        self.diffusion_steps, self.beta_scheduler = cfg.DIFFUSION_STEPS, cfg.BETA_SCHEDULER
+        self.sampling_strategy = sampling_strategy
+        self.num_frames = num_frames
+        self.precision = "fp32"
+        self.text_encoder = None
+        self.clip_heads = 8                   # CLIP ViT-B/32 text tower: width 512, 8 heads (mdm.py:72)
+        if self.nfeats != 262:
+            raise NotImplementedError(f"INPUT_DIM={self.nfeats}: the HIP path is built for 262 pose features per person")
+        self.betas = get_named_beta_schedule(self.beta_scheduler, self.diffusion_steps)
+        from .synthetic import mdm_denoiser_shapes
+        for k, shp in mdm_denoiser_shapes("model.", self.latent_dim, self.ff_size, self.num_layers).items():
+            _holder_tree(self, k, torch.zeros(shp))
+        _holder_tree(self, "embed_text.weight", torch.zeros(self.latent_dim, 512))
+        _holder_tree(self, "embed_text.bias", torch.zeros(self.latent_dim))
+        self._sampler, self._dirty = None, True
+        self._text_sd, self._text = None, None
+
+    def load_state_dict(self, state_dict, strict=True):
+        sd = _unwrap_checkpoint(state_dict)
+        clip_sd = {k: v for k, v in sd.items() if k.startswith("clip_model.")}
+        res = super().load_state_dict({k: v for k, v in sd.items() if not k.startswith("clip_model.")}, strict=strict)
+        if "clip_model.token_embedding.weight" in clip_sd:
+            self._text_sd, self._text = clip_sd, None
+        return res
+
+    def _make_sampler(self, B, T, dev):
+        return Sampler(d_latent=self.latent_dim, d_ff=self.ff_size, d_layers=self.num_layers, d_heads=self.num_heads, single_only=1, model1_kind=1,
+                       cfg_scale=self.cfg_weight, max_batch=B, max_frames=T, device=dev, precision=self.precision)
+
+    def _sampler_state(self):
+        return {"denoiser1." + k[len("model."):]: p.data for k, p in self.named_parameters() if k.startswith("model.")}
+
+    def generate_cond(self, batch):
+        """mdm.py:141-149."""
+        if "cond" in batch:
+            return batch["cond"]
+        if self.text_encoder is not None:
+            return self.text_encoder(batch)
+        if self._text_sd is None:
+            raise NotImplementedError("text encoding (MDM's CLIP ViT-B/32 + embed_text, mdm.py:100-121) is upstream of the HIP path: put the encoded 'cond' "
+                                      "[B, LATENT_DIM] in the batch, load a checkpoint that carries clip_model.*, or set model.text_encoder")
+        from .text import MdmTextHead, tokenize_mdm
+        dev = self.device
+        if self._text is None or self._text.w.device != dev:
+            sd = dict(self._text_sd)
+            sd["embed_text.weight"], sd["embed_text.bias"] = self.embed_text.weight.data, self.embed_text.bias.data
+            self._text = MdmTextHead(sd, "", self.clip_heads, dev)
+        tok = torch.as_tensor(batch["tokens_mdm_text"]) if "tokens_mdm_text" in batch else tokenize_mdm(batch["text"])
+        return self._text(tok)
+
+    def forward(self, batch, **loop_kw):
+        """mdm.py:195-228 -> {"output": [B, T, 262]}.  loop_kw (eta, seed, step_noise, x_start, init_image, skip_timesteps): handed to the library, whose
+        refusal for this mode comes back as NotImplementedError."""
+        b = dict(batch)
+        b["cond"] = self.generate_cond(batch)
+        cond, x_T, B, T = self._inputs(b)
+        s = self._get_sampler(B, T)
+        kw = {k: v for k, v in loop_kw.items() if v is not None and not (k in ("eta", "skip_timesteps") and not v)}
+        if "step_noise" in kw:
+            kw["noise"] = kw.pop("step_noise")
+        if kw.get("eta") and "noise" not in kw and "seed" not in kw:
+            kw["seed"] = 0
+        return {"output": _unsupported(s.sample, cond, x_T, **kw)}
+
+    def forward_test(self, batch):
+        return self.forward(batch)
+
+    def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
+        """Many forward calls at once over the ragged path of the single-person sampler -> one {"output": [b, T, 262]} per batch, bit-identical to the
+        sequential calls.  eta / skip_timesteps or loop arguments in the batch dicts: NotImplementedError (the library's message)."""
+        with torch.no_grad():
+            bs = []
+            for b in batches:
+                b = dict(b)
+                b["cond"] = self.generate_cond(b)
+                bs.append(b)
+        return self._sample_many(bs, batching, max_rows, max_items, eta, skip_timesteps, options=False)

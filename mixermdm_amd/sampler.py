@@ -108,7 +108,10 @@ class Sampler:
                  model1_kind=0, d1_latent=0, d1_ff=0, d1_layers=0, d1_heads=0):
         """single_only: False/0 = two-chain MixerMDM; True/1 = individual denoiser alone (2-way CFG);
         2 = interaction denoiser alone with the 4-way CFG of ClassifierFreeSampleModelMultiple;
-        3 = in2IN "dual": both denoisers composed by ClassifierFreeSampleDualMDM (call set_dual_weights after set_schedule).
+        3 = in2IN "dual": both denoisers composed by ClassifierFreeSampleDualMDM (call set_dual_weights after set_schedule);
+        4 = the InterGen denoiser alone under the 2-way CFG (needs model2_kind=1; cond [B, text_dim], x [B, T, 524]) -- the one single-chain mode whose
+        begin / sample / begin_ragged / sample_ragged(_async) and set_eta take the loop's other arguments (eta, noise | seed(s), noise_rows, x_start,
+        init_image, skip_timesteps) with the two-chain sampler's rules.
         model1_kind: 0 = in2IN individual, 1 = MDMDenoiser (precision "fp32" or "fp32_split", the latter at head sizes 64 / 128; "bf16" /
         "bf16_fp8" are refused for it); d1_*: denoiser1's own sizes (0 = same as d_*).
         precision: "fp32" (native fp32 MFMA), "fp32_split" (fp32 results from six bf16 MFMAs per product on exactly split operands:
@@ -176,7 +179,7 @@ class Sampler:
         sd = dict(sd)
         D, Dm = self.cfg.d_latent, self.cfg.m_latent
         pes = []
-        if self.single_only != 2:
+        if self.single_only not in (2, 4):
             pes.append(("denoiser1.sequence_pos_encoder.pe", self.cfg.d1_latent or D))
         if self.single_only != 1:
             pes.append(("denoiser2.sequence_pos_encoder.pe", D))
@@ -272,7 +275,7 @@ class Sampler:
 
     # ---- sampling ---------------------------------------------------------------------------------
     def begin(self, cond, x_T, *, noise=None, seed=None, x_start=None, init_image=None, skip_timesteps=0):
-        """mmdm_begin, or mmdm_begin_opts when a keyword is given (the other arguments of MixerDiffusion.ddim_sample_loop, two-chain sampler):
+        """mmdm_begin, or mmdm_begin_opts when a keyword is given (the other arguments of MixerDiffusion.ddim_sample_loop; two-chain sampler and single_only=4):
         noise [n >= S - skip, B, T, 524] = the step noises by loop position, or seed = the device generator's (ops.randn(seed, k, B, T) is step k's
         noise) -- one of them while eta > 0 (set_eta); x_start [B, T' >= T, 524] pins the roots' ground path at every step; init_image [B, T, 524] /
         skip_timesteps start the chains from q_sample(init_image, S - 1 - skip, x_T) (skip > 0 and no image: zeros) and run the steps from there."""
@@ -333,7 +336,7 @@ class Sampler:
     def begin_ragged(self, cond, x_T, lens, *, noise=None, seeds=None, noise_rows=None, x_start=None, init_image=None, skip_timesteps=0):
         """Begin a RAGGED call (mmdm_begin_ragged): B items of different lengths in one batch.  cond [B, .]; lens: B ints; x_T: the items' frames
         back to back [sum(lens), C], or a list of B tensors [T_i, C].  Every item's result is bit-identical to sampling it alone.
-        With a keyword (mmdm_begin_ragged_opts; two-chain sampler; forms and shapes: pack_ragged_options) the same holds with begin()'s options: item b of
+        With a keyword (mmdm_begin_ragged_opts; two-chain sampler and single_only=4; forms and shapes: pack_ragged_options) the same holds with begin()'s options: item b of
         seeds=[...] equals sample(cond[b:b+1], x_b[None], seed=seeds[b], ...), and seeds=ONE int makes a batch of equal lengths equal to sample(cond, x,
         seed=seed) of the uniform batch; noise / x_start / init_image are each item's own, packed or as lists."""
         lens = [int(v) for v in lens]
