@@ -615,6 +615,40 @@ def cfg_ddim(m, coef, step_idx, cfg_scale, x):
     return p
 
 
+def _pred_out(pred_xstart, x):
+    """pred_xstart of a single-chain update: True -> a new tensor, False / None -> not written, a tensor -> written in place."""
+    if pred_xstart is True:
+        return torch.empty_like(x)
+    if pred_xstart is False or pred_xstart is None:
+        return None
+    _chk(pred_xstart)
+    assert pred_xstart.shape == x.shape and pred_xstart.is_contiguous()
+    return pred_xstart
+
+
+def cfg4_ddim(m, coef, step_idx, s, s_int, s_ind, x, pred_xstart=True):
+    """mmdm_cfg4_ddim_f32: m [4B, T, C] = full | interaction-only | individuals-only | uncond rows; x [B, T, C] in place.  Returns pred_xstart (or None)."""
+    _chk(m, coef, step_idx, x)
+    B, T, Cc = x.shape
+    assert m.shape == (4 * B, T, Cc) and x.is_contiguous()
+    p = _pred_out(pred_xstart, x)
+    check(load_library().mmdm_cfg4_ddim_f32(_p(m.contiguous()), _p(coef), coef.shape[1], _p(step_idx), float(s), float(s_int), float(s_ind), _p(x), _p(p), B, T, Cc,
+                                            _stream()))
+    return p
+
+
+def dual_ddim(m_ind, m_int, coef, step_idx, w_table, s_ind, s_int, x, pred_xstart=True):
+    """mmdm_dual_ddim_f32: m_ind / m_int [2B, T, C] = cond | uncond rows of the two models, w_table [S] fp32 on the device; x [B, T, C] in place.  Returns
+    pred_xstart (or None)."""
+    _chk(m_ind, m_int, coef, step_idx, w_table, x)
+    B, T, Cc = x.shape
+    assert m_ind.shape == m_int.shape == (2 * B, T, Cc) and x.is_contiguous() and w_table.dtype == torch.float32 and w_table.numel() == coef.shape[1]
+    p = _pred_out(pred_xstart, x)
+    check(load_library().mmdm_dual_ddim_f32(_p(m_ind.contiguous()), _p(m_int.contiguous()), _p(coef), coef.shape[1], _p(step_idx), _p(w_table.contiguous()),
+                                            float(s_ind), float(s_int), _p(x), _p(p), B, T, Cc, _stream()))
+    return p
+
+
 def gaussian_filter1d(x, sigma=1.0, truncate=4.0):
     """scipy.ndimage.gaussian_filter1d(x, sigma, axis=-2, mode="nearest") for x [..., T, C] on the GPU."""
     import numpy as np

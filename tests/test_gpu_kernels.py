@@ -2,6 +2,7 @@
 
 Tolerances (fp32): GEMM-based ops atol 2e-4 * sqrt(K/1024)-ish relative to unit-variance data -> stated per test;
 geometry compared with the masked/percentile rule of tests/test_oracle_golden.py::close_frac.
+The branch points of the geometry, blend and update kernels (constructed inputs, per-case bounds, no percentile rule): tests/test_gpu_geometry.py.
 """
 import math
 import numpy as np
