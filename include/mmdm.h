@@ -535,6 +535,18 @@ typedef struct {
                         *    two-plane attention, LayerNorm / sequence assembly writing fp32 rows + planes in one pass -- needs head size 64 or
                         *    128, MDM's own 256 / 4 heads gives 64); precision 1 and 3 with model1_kind = 1 are MMDM_ERR_UNSUPPORTED */
     int d1_latent, d1_ff, d1_layers, d1_heads;   /* denoiser1's own sizes (MODEL1 is a separate config); 0 = same as d_* */
+    int cfg_form;      /* single_only == 4 only: the guidance wrapper of the one-chain sampler (any other single_only with cfg_form != 0, and a value outside
+                        *    0..2, are MMDM_ERR_ARG).
+                        * 0: ClassifierFreeSampleModel, 2-way: mode 4 as described above; model2_kind must be 1.
+                        * 1: ClassifierFreeSampleModelMultiple, 4-way (cfg_sampler.py:59-98): the sampler of single_only = 2 -- denoiser 2 alone, in2IN or
+                        *    InterGen by model2_kind, cond [B, 3*text_dim], scales cfg_scale / cfg_scale_interaction / cfg_scale_individual, the same kernels
+                        *    and bits on a plain call -- with everything mode 4 adds: mmdm_set_eta, mmdm_begin_opts, mmdm_begin_ragged(_opts).  A ragged group
+                        *    runs 4 CFG copies x 2 persons = 8 sequence groups.
+                        * 2: ClassifierFreeSampleDualMDM (cfg_sampler.py:101-150): the sampler of single_only = 3 -- denoiser 1 (in2IN, model1_kind 0) in
+                        *    "dual_individual" and denoiser 2 in "dual_interaction", cond [B, 5*text_dim], scales cfg_scale_individual /
+                        *    cfg_scale_interaction, needs mmdm_set_dual_weights -- with the same additions; the two models run on the handle's two streams.
+                        * Both: x and pred_xstart [B, T, 524]; mmdm_set_key_mask and mmdm_set_history (with a destination) refuse them as they refuse mode 4;
+                        *    mmdm_module_forward takes the `which` values of single_only = 2 / 3; every precision mode. */
 } mmdm_config;
 
 int mmdm_create(const mmdm_config* cfg, mmdm_handle* out);
@@ -578,11 +590,11 @@ int mmdm_set_norm_stats(mmdm_handle h, const float* stats_host);
  * coef [4*S] fp32 as in mmdm_xstart_ddim_f32.  Builds the per-step timestep-embedding tables. */
 int mmdm_set_schedule(mmdm_handle h, const int* timestep_map, const float* coef, int S, void* stream);
 
-/* Dual sampler only (single_only == 3): w[S] (HOST floats) = the composition weight s_composition(timestep_map[i]) of every respaced
+/* Dual sampler only (single_only == 3, or single_only == 4 with cfg_form == 2): w[S] (HOST floats) = the composition weight s_composition(timestep_map[i]) of every respaced
  * step (ClassifierFreeSampleDualMDM.weight, cfg_sampler.py:113-125).  Call after every mmdm_set_schedule. */
 int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S);
 
-/* Stochastic DDIM (eta > 0; the two-chain sampler and the stand-alone InterGen sampler, single_only 0 / 4): coef_eta_host [2*S] HOST floats = sqrt(1 - ab_prev - sigma^2) and sigma of every respaced
+/* Stochastic DDIM (eta > 0; the two-chain sampler and the one-chain sampler under each of its guidance wrappers, single_only 0 / 4 with any cfg_form): coef_eta_host [2*S] HOST floats = sqrt(1 - ab_prev - sigma^2) and sigma of every respaced
  * step, sigma = eta sqrt((1 - ab_prev) / (1 - ab)) sqrt(1 - ab / ab_prev) in fp32 (gaussian_diffusion.py:1939-1951); NULL clears it (S ignored)
  * and the update is the eta = 0 one again.  Call after mmdm_set_schedule, which resets it; it ends a begun call.  While a table is set every
  * begin must name a noise source (mmdm_begin_opts, or mmdm_begin_ragged_opts for a ragged batch; MMDM_ERR_STATE otherwise -- so mmdm_begin is refused;
@@ -590,7 +602,8 @@ int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S);
  * well.  The step then ends in
  *   x = x0 sqrt(ab_prev) + coef_eta[0][i] eps + [i != 0] coef_eta[1][i] noise        (both chains, the SAME noise [B, T, 524]; :1947-1963)
  * The call waits for the stream of the handle's last begin before it replaces the table.  single_only 1 / 2 / 3: MMDM_ERR_UNSUPPORTED.
- * single_only = 4: the one chain ends in the same form (gaussian_diffusion.py:836-848). */
+ * single_only = 4 (cfg_form 0 / 1 / 2: after the 2-way CFG, the 4-way CFG or the DualMDM combine): the one chain ends in the same form
+ * (gaussian_diffusion.py:836-848). */
 int mmdm_set_eta(mmdm_handle h, const float* coef_eta_host, int S);
 
 /* Check that every weight is present; allocate nothing afterwards. */
@@ -623,7 +636,7 @@ int mmdm_set_key_mask(mmdm_handle h, const unsigned char* valid_host, int rows, 
 int mmdm_begin(mmdm_handle h, const float* cond, const float* x_T, int B, int T, void* stream);
 
 /* mmdm_begin with the loop's other arguments (MixerDiffusion.ddim_sample_loop_progressive, gaussian_diffusion.py:1822-1899); two-chain sampler
- * and the stand-alone InterGen sampler (single_only = 4: read "the chain" for "both chains" below; gaussian_diffusion.py:999-1069),
+ * and the one-chain sampler (single_only = 4 with any cfg_form -- InterGen, and the 4-way CFG / DualMDM samplers of in2IN: read "the chain" for "both chains" below; gaussian_diffusion.py:999-1069),
  * uniform batches (ragged ones: mmdm_begin_ragged_opts).  A zeroed struct (or opts == NULL) is mmdm_begin.  Options belong to the CALL: every mmdm_begin / mmdm_begin_ragged resets
  * them, as it resets the history.  Device buffers are the caller's and must stay alive until the stream has passed the call's last step.
  *   noise_source  0 = none; 1 = `noise` [noise_steps, B, T, 524]: slot k is th.randn_like(x) of the step at loop position k (0 = the first executed
@@ -670,10 +683,10 @@ int mmdm_begin_opts(mmdm_handle h, const float* cond, const float* x_T, int B, i
  * [rows, 524] buffers whose first sum(lens) rows are the items back to back; history slots (mmdm_set_history) are [2 * rows, C] with the
  * uncond half at row `rows`; mmdm_call_rows returns (rows, sum(lens)).  Covers the two-chain sampler and the single-person sampler over
  * in2IN / InterGen denoisers with head sizes 64 / 128, every precision mode, and over MDMDenoiser as denoiser 1 (head sizes 64 / 128, fp32 and
- * fp32-split: the precisions MDM has), and the stand-alone InterGen sampler (single_only = 4); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
+ * fp32-split: the precisions MDM has), and the one-chain sampler (single_only = 4; cfg_form 1 runs 8 sequence groups, cfg_form 2 two stacks of 4); single_only 2 / 3 are MMDM_ERR_UNSUPPORTED; B <= min(max_batch, 256), sum(lens) <= max_batch * max_frames;
  * otherwise MMDM_ERR_UNSUPPORTED / MMDM_ERR_ARG.  mmdm_run / mmdm_seek / mmdm_set_history as after mmdm_begin. */
 int mmdm_begin_ragged(mmdm_handle h, const float* cond, const float* x_T, int B, const int* lens_host, void* stream);
-/* mmdm_begin_ragged with the loop's other arguments: mmdm_begin_opts for a RAGGED batch (two-chain sampler and single_only = 4; every precision mode; in2IN / InterGen
+/* mmdm_begin_ragged with the loop's other arguments: mmdm_begin_opts for a RAGGED batch (two-chain sampler and single_only = 4 with any cfg_form; every precision mode; in2IN / InterGen
  * denoisers and MDM as denoiser 1 where ragged batches cover it).  The rule of ragged batches holds with every option: each item is BIT-IDENTICAL to
  * the same item sampled alone with the same options (tests/test_gpu_ragged_opts.py).  A zeroed struct (or opts == NULL) is mmdm_begin_ragged.  Device
  * buffers are PACKED like x_T -- the items' frames back to back -- are the caller's and must stay alive until the stream has passed the call's last

@@ -33,7 +33,7 @@ class Config(C.Structure):
                [("force_val", C.c_float), ("cfg_scale", C.c_float)] + \
                [(n, C.c_int) for n in ("max_batch", "max_frames", "single_only")] + \
                [("cfg_scale_interaction", C.c_float), ("cfg_scale_individual", C.c_float), ("precision", C.c_int)] + \
-               [(n, C.c_int) for n in ("model1_kind", "d1_latent", "d1_ff", "d1_layers", "d1_heads")]
+               [(n, C.c_int) for n in ("model1_kind", "d1_latent", "d1_ff", "d1_layers", "d1_heads", "cfg_form")]
 
 
 class EncoderLayerWeights(C.Structure):

@@ -635,31 +635,86 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void cfg4_ddim_kernel(const float* __restrict__ m, const float* __restrict__ coef, int S, const int* __restrict__ step_idx,
-                                                         float s, float si, float sd, float* __restrict__ x, float* __restrict__ px, size_t per_batch_total) {
+// The same update behind the other two guidance wrappers: x0 = the wrapper's combine at element idx (a functor: its expression keeps its operation order in
+// every form), then exactly cfg_ddim_kernel's forms -- <false, 0> is the kernel the stand-alone 4-way CFG and dual samplers (single_only 2 / 3) have always
+// launched, the others serve single_only = 4 with cfg_form 1 / 2 (the loop's options, ragged groups: the further CFG copies of the model output lie
+// per_batch_total = rg.rows * C apart).
+template <bool RAG, int NOISE, typename X0, typename... NA>
+__device__ __forceinline__ void combine_ddim(const X0& x0_of, const float* __restrict__ coef, int S, const int* __restrict__ step_idx, float* __restrict__ x,
+                                             float* __restrict__ px, size_t per_batch_total, NA... na) {
+    static_assert((!RAG && NOISE == 0) ? sizeof...(NA) == 0 : (NOISE == 0 ? sizeof...(NA) == 1 : sizeof...(NA) == 2), "forms: (), (CfgRows), (CfgRows, NoiseArgs)");
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= per_batch_total) return;
     const int i = *step_idx;
-    // (s*full) + (s_int*interaction-only) + (s_ind*individuals-only) + ((1-(s+s_int+s_ind))*uncond)   cfg_sampler.py:97
-    const float x0 = (s * m[idx]) + (si * m[per_batch_total + idx]) + (sd * m[2 * per_batch_total + idx]) + ((1.0f - (s + si + sd)) * m[3 * per_batch_total + idx]);
-    x[idx] = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], coef[3 * S + i]);
-    if (px) px[idx] = x0;
+    if constexpr (!RAG && NOISE == 0) {
+        const float x0 = x0_of(idx, i);
+        x[idx] = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], coef[3 * S + i]);
+        if (px) px[idx] = x0;
+    } else {
+        const CfgRows& cr = cfg_rows_of(na...);
+        const int col = (int)(idx % cr.C);
+        const size_t fr = idx / cr.C;
+        int b, t;
+        if constexpr (RAG) {
+            b = cr.rg.row_item[fr];
+            if (b < 0) return;
+            t = cr.rg.row_pos[fr];
+        } else {
+            b = (int)(fr / cr.T);
+            t = (int)(fr % cr.T);
+        }
+        const float x0 = x0_of(idx, i);
+        if constexpr (NOISE == 0) {
+            x[idx] = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], coef[3 * S + i]);
+        } else {
+            const NoiseArgs& a = cfg_noise_of(na...);
+            float v = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], a.coef_eta[i]);
+            if (i != 0) {                                        // nonzero_mask * sigma * noise
+                const int lp = *a.loop_pos;
+                float z;
+                if constexpr (NOISE == 1) {
+                    const size_t stride = RAG ? (size_t)a.od->noise_stride : per_batch_total;
+                    z = lp < a.od->noise_steps ? a.od->noise[(size_t)lp * stride + idx] : 0.f;       // (the host refuses a run past the buffer)
+                } else if constexpr (RAG) z = step_normal(a.od->item_seed[b], lp, a.od->item_noise_row[b], t, col);
+                else z = step_normal(a.od->seed, lp, b, t, col);
+                v = __builtin_fmaf(a.coef_eta[S + i], z, v);     // (one fixed operation: every instantiation rounds alike)
+            }
+            x[idx] = v;
+        }
+        if (px) px[idx] = x0;
+    }
+}
+
+// ClassifierFreeSampleModelMultiple: (s*full) + (s_int*interaction-only) + (s_ind*individuals-only) + ((1-(s+s_int+s_ind))*uncond)   cfg_sampler.py:97
+struct Cfg4X0 {
+    const float* __restrict__ m; float s, si, sd; size_t per_batch_total;
+    __device__ __forceinline__ float operator()(size_t idx, int) const {
+        return (s * m[idx]) + (si * m[per_batch_total + idx]) + (sd * m[2 * per_batch_total + idx]) + ((1.0f - (s + si + sd)) * m[3 * per_batch_total + idx]);
+    }
+};
+template <bool RAG = false, int NOISE = 0, typename... NA>
+__global__ __launch_bounds__(256) void cfg4_ddim_kernel(const float* __restrict__ m, const float* __restrict__ coef, int S, const int* __restrict__ step_idx,
+                                                         float s, float si, float sd, float* __restrict__ x, float* __restrict__ px, size_t per_batch_total,
+                                                         NA... na) {
+    combine_ddim<RAG, NOISE>(Cfg4X0{m, s, si, sd, per_batch_total}, coef, S, step_idx, x, px, per_batch_total, na...);
 }
 
 // ClassifierFreeSampleDualMDM.forward combine (cfg_sampler.py:139-150) + DDIM update: per-model guidance, then the
 // time-scheduled blend out_int + w[step] (out_ind - out_int).
+struct DualX0 {
+    const float* __restrict__ mi; const float* __restrict__ mI; const float* __restrict__ wtab; float s_ind, s_int; size_t per_batch_total;
+    __device__ __forceinline__ float operator()(size_t idx, int i) const {
+        const float ui = mi[per_batch_total + idx], uI = mI[per_batch_total + idx];
+        const float gI = uI + s_int * (mI[idx] - uI);
+        const float gi = ui + s_ind * (mi[idx] - ui);
+        return gI + wtab[i] * (gi - gI);
+    }
+};
+template <bool RAG = false, int NOISE = 0, typename... NA>
 __global__ __launch_bounds__(256) void dual_ddim_kernel(const float* __restrict__ mi, const float* __restrict__ mI, const float* __restrict__ coef, int S,
                                                          const int* __restrict__ step_idx, const float* __restrict__ wtab, float s_ind, float s_int,
-                                                         float* __restrict__ x, float* __restrict__ px, size_t per_batch_total) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= per_batch_total) return;
-    const int i = *step_idx;
-    const float ui = mi[per_batch_total + idx], uI = mI[per_batch_total + idx];
-    const float gI = uI + s_int * (mI[idx] - uI);
-    const float gi = ui + s_ind * (mi[idx] - ui);
-    const float x0 = gI + wtab[i] * (gi - gI);
-    x[idx] = ddim(x[idx], x0, coef[i], coef[S + i], coef[2 * S + i], coef[3 * S + i]);
-    if (px) px[idx] = x0;
+                                                         float* __restrict__ x, float* __restrict__ px, size_t per_batch_total, NA... na) {
+    combine_ddim<RAG, NOISE>(DualX0{mi, mI, wtab, s_ind, s_int, per_batch_total}, coef, S, step_idx, x, px, per_batch_total, na...);
 }
 
 __global__ void step_dec_kernel(int* step_idx, int* loop_pos) { *step_idx -= 1; *loop_pos += 1; }
@@ -1086,25 +1141,61 @@ int mmdm_cfg_ddim(int form, const float* m, const float* coef, const float* coef
     return mmdm_check_launch("cfg_ddim");
 }
 
+// the six forms of one update kernel (rows uniform / ragged x noise form 0 / 1 / 2); `...` = the kernel's own arguments up to per_batch_total
+#define MMDM_LAUNCH_UPDATE_FORMS(KERNEL, ...)                                                                                                       \
+    do {                                                                                                                                            \
+        if (r.fr) {                                                                                                                                 \
+            if (form == 0) hipLaunchKernelGGL((KERNEL<true, 0, CfgRows>), grid, block, 0, st, __VA_ARGS__, total, cr);                              \
+            else if (form == 1) hipLaunchKernelGGL((KERNEL<true, 1, CfgRows, NoiseArgs>), grid, block, 0, st, __VA_ARGS__, total, cr, na);          \
+            else hipLaunchKernelGGL((KERNEL<true, 2, CfgRows, NoiseArgs>), grid, block, 0, st, __VA_ARGS__, total, cr, na);                         \
+        } else if (form == 0) hipLaunchKernelGGL((KERNEL<false, 0>), grid, block, 0, st, __VA_ARGS__, total);                                       \
+        else if (form == 1) hipLaunchKernelGGL((KERNEL<false, 1, CfgRows, NoiseArgs>), grid, block, 0, st, __VA_ARGS__, total, cr, na);             \
+        else hipLaunchKernelGGL((KERNEL<false, 2, CfgRows, NoiseArgs>), grid, block, 0, st, __VA_ARGS__, total, cr, na);                            \
+    } while (0)
+
+// The 4-way CFG update with the loop's options (single_only = 4, cfg_form = 1): form, r and C as mmdm_cfg_ddim; m holds the four CFG copies of the model
+// output one after the other (ragged: at the group stride).  Form 0 on uniform rows is mmdm_cfg4_ddim_f32's launch.
+int mmdm_cfg4_ddim(int form, const float* m, const float* coef, const float* coef_eta, int S, const int* step_idx, const int* loop_pos, const mmdm_opts_desc* od,
+                   float s, float s_int, float s_ind, float* x, float* pred_xstart, const mmdm_rows& r, int C, hipStream_t st) {
+    if (form < 0 || form > 2) return mmdm_set_error(MMDM_ERR_ARG, "cfg4_ddim: form %d", form);
+    const size_t total = (r.fr ? (size_t)r.fr->rows : (size_t)r.n * r.T) * C;
+    if (total == 0) return MMDM_OK;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    const NoiseArgs na{coef_eta, od, loop_pos};
+    const CfgRows cr{r.T, C, r.fr ? *r.fr : mmdm_rag{}};
+    MMDM_LAUNCH_UPDATE_FORMS(cfg4_ddim_kernel, m, coef, S, step_idx, s, s_int, s_ind, x, pred_xstart);
+    return mmdm_check_launch(r.fr ? "cfg4_ddim_rag" : "cfg4_ddim");
+}
+
 extern "C" int mmdm_cfg4_ddim_f32(const float* m, const float* coef, int S, const int* step_idx, float s, float s_int, float s_ind,
                                   float* x, float* pred_xstart, int B, int T, int C, void* stream) {
     if (B == 0 || T == 0) return MMDM_OK;
     if (!m || !coef || !step_idx || !x || S <= 0 || B < 0 || T < 0 || C <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_cfg4_ddim_f32: bad arguments");
-    const size_t total = (size_t)B * T * C;
-    hipLaunchKernelGGL(cfg4_ddim_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       m, coef, S, step_idx, s, s_int, s_ind, x, pred_xstart, total);
-    return mmdm_check_launch("cfg4_ddim");
+    return mmdm_cfg4_ddim(0, m, coef, nullptr, S, step_idx, nullptr, nullptr, s, s_int, s_ind, x, pred_xstart, mmdm_rows{B, T}, C, static_cast<hipStream_t>(stream));
 }
+
+// The DualMDM update with the loop's options (single_only = 4, cfg_form = 2): m_ind / m_int hold the cond | uncond halves of the two models' outputs.
+// Form 0 on uniform rows is mmdm_dual_ddim_f32's launch.
+int mmdm_dual_ddim(int form, const float* m_ind, const float* m_int, const float* coef, const float* coef_eta, int S, const int* step_idx, const int* loop_pos,
+                   const mmdm_opts_desc* od, const float* w_table, float s_ind, float s_int, float* x, float* pred_xstart, const mmdm_rows& r, int C, hipStream_t st) {
+    if (form < 0 || form > 2) return mmdm_set_error(MMDM_ERR_ARG, "dual_ddim: form %d", form);
+    const size_t total = (r.fr ? (size_t)r.fr->rows : (size_t)r.n * r.T) * C;
+    if (total == 0) return MMDM_OK;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    const NoiseArgs na{coef_eta, od, loop_pos};
+    const CfgRows cr{r.T, C, r.fr ? *r.fr : mmdm_rag{}};
+    MMDM_LAUNCH_UPDATE_FORMS(dual_ddim_kernel, m_ind, m_int, coef, S, step_idx, w_table, s_ind, s_int, x, pred_xstart);
+    return mmdm_check_launch(r.fr ? "dual_ddim_rag" : "dual_ddim");
+}
+#undef MMDM_LAUNCH_UPDATE_FORMS
 
 extern "C" int mmdm_dual_ddim_f32(const float* m_ind, const float* m_int, const float* coef, int S, const int* step_idx, const float* w_table,
                                   float s_ind, float s_int, float* x, float* pred_xstart, int B, int T, int C, void* stream) {
     if (B == 0 || T == 0) return MMDM_OK;
     if (!m_ind || !m_int || !coef || !step_idx || !w_table || !x || S <= 0 || B < 0 || T < 0 || C <= 0)
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_dual_ddim_f32: bad arguments");
-    const size_t total = (size_t)B * T * C;
-    hipLaunchKernelGGL(dual_ddim_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       m_ind, m_int, coef, S, step_idx, w_table, s_ind, s_int, x, pred_xstart, total);
-    return mmdm_check_launch("dual_ddim");
+    return mmdm_dual_ddim(0, m_ind, m_int, coef, nullptr, S, step_idx, nullptr, nullptr, w_table, s_ind, s_int, x, pred_xstart, mmdm_rows{B, T}, C,
+                          static_cast<hipStream_t>(stream));
 }
 
 // split != 0: dst receives [npers][2 planes][rows][ldp] fp16 (the A operand of mmdm_linear_split) instead of [npers][rows][ldp] fp32

@@ -146,6 +146,12 @@ int mmdm_xstart_ddim(int form, const float* model_out, const float* stats, const
 // The single-chain update (2-way CFG combine + DDIM) with the same forms, on one chain of width C = 262 or 524; form 0 on uniform rows is mmdm_cfg_ddim_f32's kernel
 int mmdm_cfg_ddim(int form, const float* m, const float* coef, const float* coef_eta, int S, const int* step_idx, const int* loop_pos, const mmdm_opts_desc* od,
                   float cfg_scale, float* x, float* pred_xstart, const mmdm_rows& r, int C, hipStream_t st);
+// The same forms behind the 4-way CFG combine (m: the four CFG copies one after the other) and the DualMDM combine (the two models' cond | uncond halves, the
+// per-step composition weights w_table); form 0 on uniform rows is the launch of mmdm_cfg4_ddim_f32 / mmdm_dual_ddim_f32
+int mmdm_cfg4_ddim(int form, const float* m, const float* coef, const float* coef_eta, int S, const int* step_idx, const int* loop_pos, const mmdm_opts_desc* od,
+                   float s, float s_int, float s_ind, float* x, float* pred_xstart, const mmdm_rows& r, int C, hipStream_t st);
+int mmdm_dual_ddim(int form, const float* m_ind, const float* m_int, const float* coef, const float* coef_eta, int S, const int* step_idx, const int* loop_pos,
+                   const mmdm_opts_desc* od, const float* w_table, float s_ind, float s_int, float* x, float* pred_xstart, const mmdm_rows& r, int C, hipStream_t st);
 // x2 == nullptr in the next two: the one-chain forms
 int mmdm_pin_root(float* x, float* x2, const mmdm_opts_desc* od, const mmdm_rows& r, hipStream_t st);
 int mmdm_q_sample(float* x, float* x2, const float* init, float a, float b, size_t total, hipStream_t st);

@@ -310,6 +310,7 @@ struct mmdm_handle_s {
     int noise_form = 0;                                    // 0 = none, 1 = the caller's buffer, 2 = the device generator: which update kernel a step launches
     bool pinned = false;                                   // x_start given: pin_root_kernel is the first node of a step
     int host_loop = 0;                                     // mirror of loop_pos
+    int lm = 0;                                            // the sampler whose step, models and buffers the handle runs (legacy_mode_of): single_only, or 2 / 3 for single_only = 4 with cfg_form 1 / 2
     int td1 = 0, cond_w = 0;                              // denoiser1's cond width (text_dim, or the latent size for MDM) and the cond row width
 
     // history: host mirror + the device-side descriptor the step's kernels read (kernels.h: mmdm_hist_desc)
@@ -346,6 +347,9 @@ namespace {
 
 // which denoisers a sampler mode holds: 2 and 4 run denoiser 2 alone, 1 runs denoiser 1 alone
 bool has_d1_of(int single_only) { return single_only != 2 && single_only != 4; }
+// single_only = 4 with a cfg_form runs the step of the stand-alone sampler under the same guidance wrapper -- 1: the 4-way CFG (2), 2: DualMDM (3) -- on the
+// one-chain infrastructure of mode 4 (the loop's options, ragged groups); every other configuration is its own mode
+int legacy_mode_of(const mmdm_config& c) { return c.single_only == 4 && c.cfg_form == 1 ? 2 : c.single_only == 4 && c.cfg_form == 2 ? 3 : c.single_only; }
 
 int herr(mmdm_handle h, int code) {
     if (code) snprintf(h->err, sizeof(h->err), "%s", g_err);
@@ -967,19 +971,19 @@ int text_rows(const Ctx& c, const ModuleW& m, const float* cond, int ldc, int co
 // blocks in the reference, so its output is the LAST block applied once to the embedded input.
 int run_dual_individual(const Ctx& c, const ModuleW& m, const float* x, int xb, int n, int T, const float* ss, int ss_ld, float* out) {
     const int D = m.st.D;
-    RC(repack(c, m, x, NF2, c.s->xp, 2, xb * T));
+    RC(repack(c, m, x, NF2, c.s->xp, 2, (int)c.rows_of(xb, T)));
     for (int p = 0; p < 2; ++p)
         for (int rep = 0; rep < n / xb; ++rep)
-            RC(embed(c, m, c.s->xp, p, c.s->h + ((size_t)p * n + (size_t)rep * xb) * T * D, xb, T));
+            RC(embed(c, m, c.s->xp, p, c.s->h + c.rows_of(p * n + rep * xb, T) * D, xb, T));
     StackRun r;
     r.nseq = n; r.T = T; r.ss = ss; r.ss_ld = ss_ld;
     r.ca_row0 = 0; r.ca_rows = n; r.ca_mode = 0; r.kv_src = nullptr;
     r.sa_row0 = r.ffn_row0 = 0; r.sa_rows = r.ffn_rows = n; r.l0 = 0;
     RC(run_stack(c, m.st, c.s->h, r));
     r.sa_row0 = r.ffn_row0 = n; r.l0 = m.st.L - 1;
-    RC(run_stack(c, m.st, c.s->h + (size_t)n * T * D, r));
+    RC(run_stack(c, m.st, c.s->h + c.rows_of(n, T) * D, r));
     for (int p = 0; p < 2; ++p)
-        RC(linear(c, c.s->h + (size_t)p * n * T * D, D, m.out_w, D, m.out_b, out + (size_t)p * NF, NF2, n * T, NF, D));
+        RC(linear(c, c.s->h + c.rows_of(p * n, T) * D, D, m.out_w, D, m.out_b, out + (size_t)p * NF, NF2, (int)c.rows_of(n, T), NF, D));
     return MMDM_OK;
 }
 
@@ -1046,8 +1050,8 @@ int run_step(const Ctx& c) {
     const int B = H->B, T = H->T, n = 2 * B;
     // the single-chain samplers run ONE stream of kernels: split the GEMMs' fractional last round (gemm_f32.hip; results are bit-identical);
     // scoped: the calling thread's stateless mmdm_linear_f32 calls keep the default rule afterwards
-    TailScope tail_scope((H->cfg.single_only == 1 || H->cfg.single_only == 2 || H->cfg.single_only == 4) ? 10 : 0);
-    if (H->cfg.single_only == 4) {   // stand-alone InterDenoiser under the 2-way CFG (intergen.py:20-213, cfg_sampler.py:12-28): one chain [B, T, 524], one emb per CFG row
+    TailScope tail_scope((H->lm == 1 || H->lm == 2 || H->lm == 4) ? 10 : 0);
+    if (H->lm == 4) {   // stand-alone InterDenoiser under the 2-way CFG (intergen.py:20-213, cfg_sampler.py:12-28): one chain [B, T, 524], one emb per CFG row
         if (H->pinned) RC(mmdm_pin_root(H->x, nullptr, H->d_opts, c.rows(B, T), c.st));
         RC(cond_vectors(c, H->d2, H->txt_d2, H->se_d2, H->ss_d2, n));
         RC(run_denoiser(c, H->d2, true, H->x, B, 2, NF2, n, T, H->ss_d2, ss_ld_of(H->d2), H->o2, NF2, true));
@@ -1066,15 +1070,17 @@ int run_step(const Ctx& c) {
         else RC(mmdm_cfg_ddim_f32(H->o1, H->d_coef, H->S, H->d_step, H->cfg.cfg_scale, H->x, H->px1, B, T, NF, c.st));
         return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
     }
-    if (H->cfg.single_only == 2) {   // stand-alone interaction denoiser, 4 CFG copies of x (cfg_sampler.py:70-71)
+    if (H->lm == 2) {   // stand-alone interaction denoiser, 4 CFG copies of x (cfg_sampler.py:70-71)
+        // (single_only = 2 itself never pins, draws noise or runs ragged: its step is the two model launches and the <false, 0> update as before)
         const int n4 = 4 * B;
+        if (H->pinned) RC(mmdm_pin_root(H->x, nullptr, H->d_opts, c.rows(B, T), c.st));
         RC(cond_vectors(c, H->d2, H->txt_d2, H->se_d2, H->ss_d2, 3 * n4));
         RC(run_denoiser(c, H->d2, true, H->x, B, 2, NF2, n4, T, H->ss_d2, ss_ld_of(H->d2), H->o2, NF2));
-        RC(mmdm_cfg4_ddim_f32(H->o2, H->d_coef, H->S, H->d_step, H->cfg.cfg_scale, H->cfg.cfg_scale_interaction, H->cfg.cfg_scale_individual,
-                              H->x, H->px1, B, T, NF2, c.st));
+        RC(mmdm_cfg4_ddim(H->noise_form, H->o2, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts, H->cfg.cfg_scale, H->cfg.cfg_scale_interaction,
+                          H->cfg.cfg_scale_individual, H->x, H->px1, c.rows(B, T), NF2, c.st));
         return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
     }
-    const bool dual = H->cfg.single_only == 3;
+    const bool dual = H->lm == 3;
     // x_start of the call (mmdm_begin_opts): both chains' root ground paths are overwritten before the models run -- the first node of the step
     if (H->pinned) RC(mmdm_pin_root(H->x, H->x2, H->d_opts, c.rows(B, T), c.st));
     // the individual model on both persons: in2IN blocks, the "dual_individual" variant of them, or MDMDenoiser
@@ -1105,8 +1111,8 @@ int run_step(const Ctx& c) {
         RC(run_denoiser(c, H->d2, true, xin2, B, 2, NF2, n, T, H->ss_d2, ss_ld_of(H->d2), H->o2, NF2));
     }
     if (dual) {
-        RC(mmdm_dual_ddim_f32(H->o1, H->o2, H->d_coef, H->S, H->d_step, H->dual_w, H->cfg.cfg_scale_individual, H->cfg.cfg_scale_interaction,
-                              H->x, H->px1, B, T, NF2, c.st));
+        RC(mmdm_dual_ddim(H->noise_form, H->o1, H->o2, H->d_coef, H->d_coef_eta, H->S, H->d_step, H->d_step + 1, H->d_opts, H->dual_w, H->cfg.cfg_scale_individual,
+                          H->cfg.cfg_scale_interaction, H->x, H->px1, c.rows(B, T), NF2, c.st));
         return mmdm_step_dec(H->d_step, H->d_step + 1, c.st);
     }
     RC(mixer_core(c, B, T));
@@ -1129,7 +1135,7 @@ int text_all(const Ctx& c, const float* cond, int n) {
     RC(text_rows(c, H->d2, cond, ldc, ig ? 0 : 1 * td, H->txt_d2, 0, n));
     RC(text_rows(c, H->d2, cond, ldc, ig ? 0 : 2 * td, H->txt_d2, n, n));
     RC(text_rows(c, H->d2, cond, ldc, 0, H->txt_d2, 2 * n, n));
-    if (H->cfg.single_only == 3) return MMDM_OK;       // dual: cond is [n, 5*td], no mixer
+    if (H->lm == 3) return MMDM_OK;       // dual: cond is [n, 5*td], no mixer
     // mixer rows: [cond_i1 | cond_i2 | cond_I] (mixermdm.py:677-682)
     RC(text_rows(c, H->mx, cond, ldc, base + td, H->txt_mx, 0, n));
     RC(text_rows(c, H->mx, cond, ldc, base + 2 * td, H->txt_mx, n, n));
@@ -1213,8 +1219,15 @@ extern "C" const char* mmdm_handle_error(mmdm_handle h) { return h ? h->err : "n
 static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* out) {
     if (!cfg || !out) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: null argument");
     if (cfg->nfeats != NF) return mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_create: nfeats must be 262");
-    const int so = cfg->single_only;
-    if (so < 0 || so > 4) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: single_only must be 0, 1, 2, 3 or 4");
+    if (cfg->single_only < 0 || cfg->single_only > 4) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: single_only must be 0, 1, 2, 3 or 4");
+    if (cfg->cfg_form < 0 || cfg->cfg_form > 2)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: cfg_form must be 0 (2-way CFG), 1 (4-way CFG) or 2 (DualMDM), got cfg_form = %d", cfg->cfg_form);
+    if (cfg->cfg_form != 0 && cfg->single_only != 4)
+        return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: cfg_form = %d selects the guidance wrapper of the one-chain sampler and needs single_only = 4, got single_only = %d",
+                              cfg->cfg_form, cfg->single_only);
+    // from here on `so` is the sampler whose models and buffers the handle holds; what only mode 4 has (the loop's options, ragged groups) asks one_chain
+    const int so = legacy_mode_of(*cfg);
+    const bool one_chain = cfg->single_only == 4;
     if (so == 4 && cfg->model2_kind != 1)
         return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create: single_only = 4 is the stand-alone InterGen sampler and needs model2_kind = 1 (InterDenoiser), got model2_kind = %d", cfg->model2_kind);
     const bool has_d1 = has_d1_of(so), has_d2 = so != 1, has_mx = so == 0, two_models = so == 0 || so == 3;
@@ -1249,6 +1262,7 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
     RC(mmdm_kernels_init());
     mmdm_handle h = new mmdm_handle_s();
     h->cfg = *cfg;
+    h->lm = so;
     if (hipGetDevice(&h->device) != hipSuccess) { delete h; return mmdm_set_error(MMDM_ERR_HIP, "mmdm_create: hipGetDevice failed"); }
     if (parent && parent->device != h->device) { delete h; return mmdm_set_error(MMDM_ERR_ARG, "mmdm_create_shared: the parent handle lives on device %d, the current device is %d", parent->device, h->device); }
     const mmdm_config& c = h->cfg;
@@ -1370,9 +1384,10 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
         h->d_klast = reinterpret_cast<int*>(tmp);
     }
     if (const char* e = getenv("MMDM_GRAPH_CACHE")) { long v = atol(e); if (v >= 1 && v <= 64) h->graph_cap = (size_t)v; }
-    // ragged calls (mmdm_begin_ragged): row maps for up to 4 groups of max_batch * max_frames rows, and per module the PE rows of a group
-    if (so <= 1 || so == 4) {
-        const size_t cap = (size_t)B * T, nb = (size_t)(B < MMDM_RAG_MAX_ITEMS ? B : MMDM_RAG_MAX_ITEMS), G = 4;
+    // ragged calls (mmdm_begin_ragged): row maps for up to 4 groups of max_batch * max_frames rows (8 under the 4-way CFG: 4 CFG copies x 2 persons), and per
+    // module the PE rows of a group
+    if (so <= 1 || one_chain) {
+        const size_t cap = (size_t)B * T, nb = (size_t)(B < MMDM_RAG_MAX_ITEMS ? B : MMDM_RAG_MAX_ITEMS), G = so == 2 ? 8 : 4;
         if ((rc = dalloc(h, &tmp, 3 * nb + 2 * cap + G * cap + 2 * G * nb))) return fail(rc);
         h->d_rag = reinterpret_cast<int*>(tmp);
         h->d_item_off = h->d_rag; h->d_item_len = h->d_item_off + nb; h->d_row_item = h->d_item_len + nb; h->d_row_pos = h->d_row_item + cap;
@@ -1387,7 +1402,7 @@ static int create_impl(const mmdm_config* cfg, mmdm_handle parent, mmdm_handle* 
             h->d_tok_item_off = h->d_tok; h->d_tok_item_len = h->d_tok_item_off + nb; h->d_tok_row_item = h->d_tok_item_len + nb;
             h->d_tok_row_pos = h->d_tok_row_item + tcap; h->d_tok_seq_off = h->d_tok_row_pos + tcap; h->d_tok_seq_len = h->d_tok_seq_off + G * nb;
         }
-        if (so == 0 || so == 4) {      // per-item generator identity (8-byte seeds first: the allocation's own alignment serves them)
+        if (so == 0 || one_chain) {      // per-item generator identity (8-byte seeds first: the allocation's own alignment serves them)
             if ((rc = dalloc(h, &tmp, 3 * (size_t)MMDM_RAG_MAX_ITEMS))) return fail(rc);
             h->d_item_seed = reinterpret_cast<unsigned long long*>(tmp);
             h->d_item_noise_row = reinterpret_cast<int*>(h->d_item_seed + MMDM_RAG_MAX_ITEMS);
@@ -1601,8 +1616,8 @@ extern "C" int mmdm_set_schedule(mmdm_handle h, const int* timestep_map, const f
     // cached step graphs stay valid: S is part of their key, the tables are device data at fixed addresses
     Ctx c{h, st, &h->sa};
     ProfPause pause(h->prof);
-    int rc = has_d1_of(h->cfg.single_only) ? build_time_tab(c, h->d1) : MMDM_OK;
-    if (!rc && h->cfg.single_only != 1) rc = build_time_tab(c, h->d2);
+    int rc = has_d1_of(h->lm) ? build_time_tab(c, h->d1) : MMDM_OK;
+    if (!rc && h->lm != 1) rc = build_time_tab(c, h->d2);
     if (!rc && h->cfg.single_only == 0) rc = build_time_tab(c, h->mx);
     h->begun = false;
     return herr(h, rc);
@@ -1610,7 +1625,7 @@ extern "C" int mmdm_set_schedule(mmdm_handle h, const int* timestep_map, const f
 
 extern "C" int mmdm_set_dual_weights(mmdm_handle h, const float* w_host, int S) {
     if (!h || !w_host) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_dual_weights: null argument");
-    if (h->cfg.single_only != 3) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_set_dual_weights: the handle is not a dual sampler (single_only != 3)"));
+    if (h->lm != 3) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_set_dual_weights: the handle is not a dual sampler (single_only != 3)"));
     if (S != h->S || S <= 0) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_set_dual_weights: S=%d does not match the schedule (%d steps)", S, h->S));
     HIPCHK(hipMemcpy(h->dual_w, w_host, (size_t)S * sizeof(float), hipMemcpyHostToDevice));
     h->dual_w_set = true;
@@ -1667,7 +1682,7 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
     if (lens) {
         if ((h->cfg.single_only > 1 && h->cfg.single_only != 4) || !h->d_rag || (h->d1.kind == 1 && !h->d_tok))
             return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: ragged batches cover the two-chain MixerMDM sampler and the single-person sampler over in2IN / InterGen / MDM denoisers"));
-        const StackW* sts[3] = {has_d1_of(h->cfg.single_only) ? &h->d1.st : nullptr, h->cfg.single_only != 1 ? &h->d2.st : nullptr, h->cfg.single_only == 0 ? &h->mx.st : nullptr};
+        const StackW* sts[3] = {has_d1_of(h->lm) ? &h->d1.st : nullptr, h->lm != 1 ? &h->d2.st : nullptr, h->lm == 0 ? &h->mx.st : nullptr};
         for (const StackW* w : sts)
             if (w && w->D / w->H != 64 && w->D / w->H != 128)
                 return herr(h, mmdm_set_error(MMDM_ERR_UNSUPPORTED, "mmdm_begin_ragged: head size %d (the ragged attention kernels cover 64 and 128)", w->D / w->H));
@@ -1715,7 +1730,7 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
         return MMDM_OK;
     };
     if (g.rag) {
-        RC(herr(h, mmdm_rag_setup(lens, B, g.rows, 4, h->d_item_off, h->d_item_len, h->d_row_item, h->d_row_pos, h->d_row_seq, h->d_seq_off, h->d_seq_len, h->d_item_order, st)));
+        RC(herr(h, mmdm_rag_setup(lens, B, g.rows, h->lm == 2 ? 8 : 4, h->d_item_off, h->d_item_len, h->d_row_item, h->d_row_pos, h->d_row_seq, h->d_seq_off, h->d_seq_len, h->d_item_order, st)));
         // (MDMDenoiser: frame t takes pe[1 + t] -- row 0 belongs to the conditioning token)
         for (ModuleW* m : {&h->d1, &h->d2, &h->mx})
             if (m->pe_r && m->pe) RC(herr(h, mmdm_gather_rows(m->pe + (m->kind == 1 ? m->st.D : 0), h->d_row_pos, m->pe_r, g.rows, m->st.D, st)));
@@ -1726,16 +1741,16 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
                                       h->d_tok_seq_len, nullptr, st)));
         }
     }
-    if (h->cfg.single_only == 3 && !h->dual_w_set) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_begin: call mmdm_set_dual_weights after mmdm_set_schedule"));
+    if (h->lm == 3 && !h->dual_w_set) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_begin: call mmdm_set_dual_weights after mmdm_set_schedule"));
     ProfPause pause(h->prof);
     int rc = MMDM_OK;
-    if (h->cfg.single_only == 4) {
+    if (h->lm == 4) {
         // cond [B, td], CFG-doubled with a zero uncond half (cfg_sampler.py:19-23); InterDenoiser has ONE emb (intergen.py:266): one text embedding per CFG row
         HIPCHK(hipMemsetAsync(h->cond_cat, 0, (size_t)n * td * sizeof(float), st));
         HIPCHK(hipMemcpyAsync(h->cond_cat, cond, (size_t)B * td * sizeof(float), hipMemcpyDeviceToDevice, st));
         rc = text_rows(c, h->d2, h->cond_cat, td, 0, h->txt_d2, 0, n);
         RC(load_x(h->x, NF2));
-    } else if (h->cfg.single_only == 2) {
+    } else if (h->lm == 2) {
         // 4 CFG copies of cond [B, 3*td]: full | interaction only (first td columns) | individuals only (columns td..) | zeros
         const int n4 = 4 * B, ldc = 3 * td;
         HIPCHK(hipMemsetAsync(h->cond_cat, 0, (size_t)n4 * ldc * sizeof(float), st));
@@ -1747,8 +1762,8 @@ static int begin_impl(mmdm_handle h, const float* cond, const float* x_T, int B,
         rc = text_rows(c, h->d2, h->cond_cat, ldc, ig ? 0 : td, h->txt_d2, 0, n4);
         if (!rc) rc = text_rows(c, h->d2, h->cond_cat, ldc, ig ? 0 : 2 * td, h->txt_d2, n4, n4);
         if (!rc) rc = text_rows(c, h->d2, h->cond_cat, ldc, 0, h->txt_d2, 2 * n4, n4);
-        HIPCHK(hipMemcpyAsync(h->x, x_T, (size_t)B * T * NF2 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    } else if (h->cfg.single_only == 1) {
+        RC(load_x(h->x, NF2));
+    } else if (h->lm == 1) {
         const int cw = h->cond_w;                            // text_dim, or the latent size for MDMDenoiser (cond is added to the timestep embedding)
         HIPCHK(hipMemsetAsync(h->cond_cat, 0, (size_t)n * cw * sizeof(float), st));
         HIPCHK(hipMemcpyAsync(h->cond_cat, cond, (size_t)B * cw * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1963,7 +1978,7 @@ extern "C" int mmdm_module_forward(mmdm_handle h, int which, const float* x, con
                                    float* out, int n, int T, void* stream) {
     if (!h || !x || !cond || !out) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_module_forward: null argument");
     if (!h->prepared) return herr(h, mmdm_set_error(MMDM_ERR_STATE, "mmdm_module_forward: call mmdm_prepare first"));
-    const int so_ = h->cfg.single_only;
+    const int so_ = h->lm;                       // (single_only = 4 with a cfg_form: the modules of the matching stand-alone sampler)
     const bool cfgx2 = which == 4;               // ClassifierFreeSampleModelX2.forward: n = B rows in, B rows out
     if (cfgx2) {
         if (so_ != 0) return herr(h, mmdm_set_error(MMDM_ERR_ARG, "mmdm_module_forward: module 4 (CFG x2) needs the two-chain handle"));

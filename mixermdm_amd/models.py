@@ -691,7 +691,11 @@ class in2INDiffusion(nn.Module):
     """Stand-alone sub-model sampler: in2INDiffusion.forward (src/models/in2in.py:285-356), modes "individual"
     (ClassifierFreeSampleModel, [B,T,262]), "interaction" (ClassifierFreeSampleModelMultiple, [B,T,524]) and "dual"
     (ClassifierFreeSampleDualMDM over net_individual + net_interaction, [B,T,524]); output stays in the model's normalised
-    space, as in the reference (callers de-normalise: src/scripts/infer/in2IN.py:101-105)."""
+    space, as in the reference (callers de-normalise: src/scripts/infer/in2IN.py:101-105).
+    Handles, one at a time: "interaction" / "dual" run on ``Sampler(single_only=4, cfg_form=1 / 2)`` -- the samplers of single_only 2 / 3 bit for bit, with
+    the loop's other arguments (GaussianDiffusion.ddim_sample_loop, gaussian_diffusion.py:946-1069) and ragged batches -- except a call with an explicit
+    ``mask``, which builds the single_only 2 / 3 handle and gets its refusal by name; "individual" stays on single_only=1, whose refusal of the loop's
+    arguments comes back as NotImplementedError.  ``.precision`` picks the handle's mode."""
 
     def __init__(self, cfg, mode, sampling_strategy="ddim50"):
         super().__init__()
@@ -709,6 +713,10 @@ class in2INDiffusion(nn.Module):
         self.diffusion_steps = cfg.DIFFUSION_STEPS
         self.betas = get_named_beta_schedule(cfg.BETA_SCHEDULER, self.diffusion_steps)
         self.sampling_strategy = sampling_strategy
+        self.beta_scheduler = cfg.BETA_SCHEDULER
+        self.num_frames = 300
+        self.precision = "fp32"
+        self.WIDTH = self.nfeats * (1 if mode == "individual" else 2)
         self._nets = {"individual": [("net_individual", "denoiser1.")], "interaction": [("net_interaction", "denoiser2.")],
                       "dual": [("net_individual", "denoiser1."), ("net_interaction", "denoiser2.")]}[mode]
         from .synthetic import denoiser_shapes
@@ -726,17 +734,27 @@ class in2INDiffusion(nn.Module):
         self._dirty = True
         return super().load_state_dict(sd, strict=strict)
 
-    def _get_sampler(self, B, T):
-        dev = next(self.parameters()).device
+    @property
+    def device(self):
+        return next(self.parameters()).device
+
+    def _get_sampler(self, B, T, legacy=False):
+        """The handle of the mode, loaded and on the model's schedule.  legacy: the single_only 2 / 3 handle of "interaction" / "dual" (a call with a mask)."""
+        dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("in2IN runs on an MI355X only: call .to('cuda:N') first (no CPU path)")
+        kind = {"individual": dict(single_only=1), "interaction": dict(single_only=2) if legacy else dict(single_only=4, cfg_form=1),
+                "dual": dict(single_only=3) if legacy else dict(single_only=4, cfg_form=2)}[self.mode]
         s = self._sampler
-        if s is None or B > s.cfg.max_batch or T > s.cfg.max_frames or s.device != dev:
+        same = s is not None and s._kind == (kind, self.precision)
+        if not same or B > s.cfg.max_batch or T > s.cfg.max_frames or s.device != dev:
+            grow = s.cfg.max_batch if same else 1
             if s is not None:
                 s.close()
-            kind = {"individual": 1, "interaction": 2, "dual": 3}[self.mode]
-            s = Sampler(d_heads=self.num_heads, single_only=kind, cfg_scale=self.cfg_weight, cfg_scale_interaction=self.cfg_weight_interaction,
-                        cfg_scale_individual=self.cfg_weight_individual, max_batch=B, max_frames=max(T, 300), device=dev, **self.dims)
+            s = Sampler(d_heads=self.num_heads, cfg_scale=self.cfg_weight, cfg_scale_interaction=self.cfg_weight_interaction,
+                        cfg_scale_individual=self.cfg_weight_individual, max_batch=max(B, grow), max_frames=max(T, self.num_frames), device=dev,
+                        precision=self.precision, **kind, **self.dims)
+            s._kind = (kind, self.precision)
             self._sampler, self._dirty = s, True
         if self._dirty:
             sd = {}
@@ -746,11 +764,14 @@ class in2INDiffusion(nn.Module):
             s.prepare()
             s._strategy = None
             self._dirty = False
+        if s._strategy != self.sampling_strategy:
+            s.set_schedule(self.sampling_strategy, self.beta_scheduler, self.diffusion_steps)
+            if self.mode == "dual":
+                s.set_dual_weights(self.cfg_composition_weight_func, self.cfg_composition_weight_value)
+            s._strategy = self.sampling_strategy
         return s
 
-    def forward(self, batch, mask=None):
-        """mask: None as the reference's forward hard-codes (in2in.py:326, 338, 350; a "mask" entry of the batch is never read), or the
-        float [B, T, k] key-padding mask for the loop's model_kwargs -- an explicit argument of this port, mode "individual" only."""
+    def _inputs(self, batch):
         if self.mode == "dual":                      # in2in.py:299-305
             cond = torch.cat([batch["cond_interaction"], batch["cond_interaction_individual1"], batch["cond_interaction_individual2"],
                               batch["cond_individual_individual1"], batch["cond_individual_individual2"]], dim=1)
@@ -759,16 +780,27 @@ class in2INDiffusion(nn.Module):
         else:
             cond = torch.cat([batch["cond_individual_individual1"]], dim=1)
         B, T = cond.shape[0], int(batch["motion_lens"][0])
-        s = self._get_sampler(B, T)
-        if s._strategy != self.sampling_strategy:
-            s.set_schedule(self.sampling_strategy, self.cfg.BETA_SCHEDULER, self.diffusion_steps)
-            if self.mode == "dual":
-                s.set_dual_weights(self.cfg_composition_weight_func, self.cfg_composition_weight_value)
-            s._strategy = self.sampling_strategy
-        width = self.nfeats * (1 if self.mode == "individual" else 2)
-        x_T = batch["x_T"] if "x_T" in batch else torch.randn(B, T, width, device=s.device)
-        with _KeyMask(s, mask):                      # model_kwargs = {"mask": mask, "cond": cond} of the loop
-            return {"output": s.sample(cond, x_T)}
+        x_T = batch["x_T"] if batch.get("x_T") is not None else torch.randn(B, T, self.WIDTH, device=self.device)
+        if tuple(x_T.shape) != (B, T, self.WIDTH):
+            raise ValueError(f"in2INDiffusion: x_T [{B}, {T}, {self.WIDTH}] expected, got {tuple(x_T.shape)}")
+        return cond, x_T, B, T
+
+    def forward(self, batch, mask=None, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0):
+        """mask: None as the reference's forward hard-codes (in2in.py:326, 338, 350; a "mask" entry of the batch is never read), or the
+        float [B, T, k] key-padding mask for the loop's model_kwargs -- an explicit argument of this port, mode "individual" only.
+        The other keywords are the loop's (InterDiffusion.forward's rules): modes "interaction" and "dual"."""
+        cond, x_T, B, T = self._inputs(batch)
+        loop_kw = dict(eta=eta, seed=seed, step_noise=step_noise, x_start=x_start, init_image=init_image, skip_timesteps=skip_timesteps)
+        if mask is not None or self.mode == "individual":
+            s = self._get_sampler(B, T, legacy=mask is not None)
+            with _KeyMask(s, mask):                  # model_kwargs = {"mask": mask, "cond": cond} of the loop
+                return {"output": _refusable_loop_call(s, cond, x_T, loop_kw)}
+        return {"output": _loop_call(self._get_sampler(B, T), cond, x_T, **loop_kw)}
+
+    def sample_many(self, batches, batching="ragged", max_rows=4800, max_items=64, *, eta=0.0, skip_timesteps=0):
+        """InterDiffusion.sample_many for this model: batch dicts as forward takes them, every motion bit-identical to that batch's own forward call.
+        Mode "individual" runs ragged without the loop's options (NotImplementedError with the library's message otherwise)."""
+        return _StandaloneDiffusion._sample_many(self, batches, batching, max_rows, max_items, eta, skip_timesteps, options=self.mode != "individual")
 
 
 class in2IN(nn.Module):
@@ -827,6 +859,12 @@ class in2IN(nn.Module):
         return batch
 
     def forward_test(self, batch):
+        batch = self._text_all(batch)
+        batch.update(self.decode_motion(batch))
+        return batch
+
+    def _text_all(self, batch):
+        """forward_test's text stage: the cond_* entries of the mode"""
         if self.mode in ("interaction", "dual"):
             batch = self.text_process(batch, "interaction", out_name="cond_interaction")
             batch = self.text_process(batch, "interaction", "text_individual1", "cond_interaction_individual1")
@@ -836,8 +874,14 @@ class in2IN(nn.Module):
             batch = self.text_process(batch, "individual", "text_individual2", "cond_individual_individual2")
         elif self.mode == "individual":
             batch = self.text_process(batch, "individual", out_name="cond_individual_individual1")
-        batch.update(self.decode_motion(batch))
         return batch
+
+    def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
+        """in2INDiffusion.sample_many after forward_test's text stage; mode / inflight / keep_history are accepted for generate_for_evaluation's call and
+        unused (one chain, no history side outputs)."""
+        with torch.no_grad():
+            batches = [self._text_all(dict(b)) for b in batches]
+        return self.decoder.sample_many(batches, batching=batching, max_rows=max_rows, max_items=max_items, eta=eta, skip_timesteps=skip_timesteps)
 
 
 # ---- stand-alone InterGen and MDM samplers ---------------------------------------------------------------------------------------
@@ -881,6 +925,40 @@ def _loop_forms(batches, eta, who):
             if f == "seed":
                 seeds[i] = int(sd) if sd is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
     return form, seeds
+
+
+def _loop_call(s, cond, x_T, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0):
+    """One sampling call with the loop's other arguments on a sampler that takes them (single_only 0 / 4).  eta > 0 needs its step noise: step_noise
+    [>= S - skip, B, T, 524] or seed (the device generator; with neither, a seed is drawn from torch's default generator).  eta belongs to the call."""
+    eta = float(eta)
+    if eta < 0:
+        raise ValueError(f"eta={eta} must be >= 0")
+    if step_noise is not None and seed is not None:
+        raise ValueError("give the step noise as a buffer (step_noise=) or as a seed (seed=), not both")
+    if eta == 0.0:
+        step_noise = seed = None
+    elif step_noise is None and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    S, skip = s.schedule.num_timesteps, int(skip_timesteps)
+    if not 0 <= skip < S:
+        raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
+    try:
+        return s.sample(cond, x_T, eta=eta, noise=step_noise[:S - skip] if step_noise is not None else None, seed=seed, x_start=x_start,
+                        init_image=init_image, skip_timesteps=skip)
+    finally:
+        if eta:
+            s.set_eta(0.0)
+
+
+def _refusable_loop_call(s, cond, x_T, loop_kw):
+    """The same call on a sampler that refuses the loop's arguments (single_only 1 / 2 / 3): whatever is given is handed to the library, whose refusal
+    comes back as NotImplementedError with its message."""
+    kw = {k: v for k, v in loop_kw.items() if v is not None and not (k in ("eta", "skip_timesteps") and not v)}
+    if "step_noise" in kw:
+        kw["noise"] = kw.pop("step_noise")
+    if kw.get("eta") and "noise" not in kw and "seed" not in kw:
+        kw["seed"] = 0
+    return _unsupported(s.sample, cond, x_T, **kw)
 
 
 class _StandaloneDiffusion(nn.Module):
@@ -1045,26 +1123,8 @@ class InterDiffusion(_StandaloneDiffusion):
         """intergen.py:184-213 -> {"output": [B, T, 524]}.  eta > 0 needs its step noise: step_noise [>= S - skip, B, T, 524] or seed (the device generator;
         with neither, a seed is drawn from torch's default generator)."""
         cond, x_T, B, T = self._inputs(batch)
-        eta = float(eta)
-        if eta < 0:
-            raise ValueError(f"eta={eta} must be >= 0")
-        if step_noise is not None and seed is not None:
-            raise ValueError("give the step noise as a buffer (step_noise=) or as a seed (seed=), not both")
-        if eta == 0.0:
-            step_noise = seed = None
-        elif step_noise is None and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        s = self._get_sampler(B, T)
-        S, skip = s.schedule.num_timesteps, int(skip_timesteps)
-        if not 0 <= skip < S:
-            raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
-        try:
-            out = s.sample(cond, x_T, eta=eta, noise=step_noise[:S - skip] if step_noise is not None else None, seed=seed, x_start=x_start,
-                           init_image=init_image, skip_timesteps=skip)
-        finally:
-            if eta:                                  # eta belongs to this call
-                s.set_eta(0.0)
-        return {"output": out}
+        return {"output": _loop_call(self._get_sampler(B, T), cond, x_T, eta=eta, seed=seed, step_noise=step_noise, x_start=x_start, init_image=init_image,
+                                     skip_timesteps=skip_timesteps)}
 
     def sample_many(self, batches, batching="ragged", max_rows=4800, max_items=64, *, eta=0.0, skip_timesteps=0):
         """Many forward calls at once (batch dicts with 'cond' [b, 768], 'motion_lens', optionally 'x_T' [b, T, 524]) -> one {"output"} per batch, every
@@ -1220,13 +1280,7 @@ class MDM(_StandaloneDiffusion):
         b = dict(batch)
         b["cond"] = self.generate_cond(batch)
         cond, x_T, B, T = self._inputs(b)
-        s = self._get_sampler(B, T)
-        kw = {k: v for k, v in loop_kw.items() if v is not None and not (k in ("eta", "skip_timesteps") and not v)}
-        if "step_noise" in kw:
-            kw["noise"] = kw.pop("step_noise")
-        if kw.get("eta") and "noise" not in kw and "seed" not in kw:
-            kw["seed"] = 0
-        return {"output": _unsupported(s.sample, cond, x_T, **kw)}
+        return {"output": _refusable_loop_call(self._get_sampler(B, T), cond, x_T, loop_kw)}
 
     def forward_test(self, batch):
         return self.forward(batch)

@@ -105,13 +105,16 @@ class Sampler:
     def __init__(self, *, d_latent, d_ff, d_layers, d_heads, m_latent=0, m_ff=0, m_layers=0, m_heads=1, mixing_mode=4, align=True,
                  xstart_align=True, model2_kind=0, force_influence_val=None, cfg_scale=3.5, max_batch=1, max_frames=300,
                  single_only=False, text_dim=768, device=None, cfg_scale_interaction=0.0, cfg_scale_individual=0.0, precision="fp32",
-                 model1_kind=0, d1_latent=0, d1_ff=0, d1_layers=0, d1_heads=0):
+                 model1_kind=0, d1_latent=0, d1_ff=0, d1_layers=0, d1_heads=0, cfg_form=0):
         """single_only: False/0 = two-chain MixerMDM; True/1 = individual denoiser alone (2-way CFG);
         2 = interaction denoiser alone with the 4-way CFG of ClassifierFreeSampleModelMultiple;
         3 = in2IN "dual": both denoisers composed by ClassifierFreeSampleDualMDM (call set_dual_weights after set_schedule);
         4 = the InterGen denoiser alone under the 2-way CFG (needs model2_kind=1; cond [B, text_dim], x [B, T, 524]) -- the one single-chain mode whose
         begin / sample / begin_ragged / sample_ragged(_async) and set_eta take the loop's other arguments (eta, noise | seed(s), noise_rows, x_start,
         init_image, skip_timesteps) with the two-chain sampler's rules.
+        cfg_form (single_only=4 only): the guidance wrapper of that one-chain sampler.  0 = the 2-way CFG above; 1 = the 4-way CFG of single_only=2
+        (denoiser 2 alone, in2IN or InterGen by model2_kind; cond [B, 3*text_dim]); 2 = DualMDM as single_only=3 (cond [B, 5*text_dim]; set_dual_weights
+        after set_schedule).  Forms 1 / 2 sample what single_only 2 / 3 sample, bit for bit, and take the loop's arguments and ragged batches as well.
         model1_kind: 0 = in2IN individual, 1 = MDMDenoiser (precision "fp32" or "fp32_split", the latter at head sizes 64 / 128; "bf16" /
         "bf16_fp8" are refused for it); d1_*: denoiser1's own sizes (0 = same as d_*).
         precision: "fp32" (native fp32 MFMA), "fp32_split" (fp32 results from six bf16 MFMAs per product on exactly split operands:
@@ -124,7 +127,8 @@ class Sampler:
         self.cfg = Config(d_latent, d_ff, d_layers, d_heads, m_latent, m_ff, m_layers, m_heads, 262, text_dim, mixing_mode, int(align),
                           int(xstart_align), model2_kind, int(force_influence_val is not None), float(force_influence_val or 0.0),
                           float(cfg_scale), max_batch, max_frames, int(single_only), float(cfg_scale_interaction), float(cfg_scale_individual),
-                          {"fp32": 0, "bf16": 1, "fp32_split": 2, "bf16_fp8": 3}[precision], int(model1_kind), d1_latent, d1_ff, d1_layers, d1_heads)
+                          {"fp32": 0, "bf16": 1, "fp32_split": 2, "bf16_fp8": 3}[precision], int(model1_kind), d1_latent, d1_ff, d1_layers, d1_heads,
+                          int(cfg_form))
         self.single_only = int(single_only)
         self.h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -179,7 +183,7 @@ class Sampler:
         sd = dict(sd)
         D, Dm = self.cfg.d_latent, self.cfg.m_latent
         pes = []
-        if self.single_only not in (2, 4):
+        if self.single_only not in (2, 4) or self.cfg.cfg_form == 2:
             pes.append(("denoiser1.sequence_pos_encoder.pe", self.cfg.d1_latent or D))
         if self.single_only != 1:
             pes.append(("denoiser2.sequence_pos_encoder.pe", D))
@@ -274,6 +278,12 @@ class Sampler:
         return self
 
     # ---- sampling ---------------------------------------------------------------------------------
+    def _check_cond(self, who, cond):
+        """cfg_form 1 / 2: the handle reads 3 / 5 text slices per cond row -- a narrower tensor would be read past its end"""
+        k = {1: 3, 2: 5}.get(self.cfg.cfg_form)
+        if k is not None and (cond.dim() != 2 or cond.shape[1] != k * self.cfg.text_dim):
+            raise ValueError(f"{who}: cfg_form={self.cfg.cfg_form} takes cond [B, {k} * text_dim = {k * self.cfg.text_dim}], got {tuple(cond.shape)}")
+
     def begin(self, cond, x_T, *, noise=None, seed=None, x_start=None, init_image=None, skip_timesteps=0):
         """mmdm_begin, or mmdm_begin_opts when a keyword is given (the other arguments of MixerDiffusion.ddim_sample_loop; two-chain sampler and single_only=4):
         noise [n >= S - skip, B, T, 524] = the step noises by loop position, or seed = the device generator's (ops.randn(seed, k, B, T) is step k's
@@ -281,6 +291,7 @@ class Sampler:
         skip_timesteps start the chains from q_sample(init_image, S - 1 - skip, x_T) (skip > 0 and no image: zeros) and run the steps from there."""
         cond = cond.to(self.device, torch.float32).contiguous()
         x_T = x_T.to(self.device, torch.float32).contiguous()
+        self._check_cond("begin", cond)
         B, T = x_T.shape[:2]
         S = self.schedule.num_timesteps
         skip = int(skip_timesteps)
@@ -348,6 +359,7 @@ class Sampler:
         cond = cond.to(self.device, torch.float32).contiguous()
         x_T = x_T.to(self.device, torch.float32).contiguous()
         B = len(lens)
+        self._check_cond("begin_ragged", cond)
         if cond.shape[0] != B or x_T.dim() != 2 or x_T.shape[0] != sum(lens):
             raise ValueError(f"begin_ragged: cond rows {cond.shape[0]}, x_T {tuple(x_T.shape)} do not match {B} items of {sum(lens)} frames in all")
         keep = [cond, x_T]

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Items/s of the stand-alone InterGen and MDM samplers: the per-item forward_test loop against ragged batches.
+"""Items/s of the stand-alone InterGen, MDM and in2IN samplers: the per-item forward_test loop against ragged batches (DESIGN sections 9d, 9e).
 
 The reference samples these models one item at a time (src/scripts/infer/mdm.py; InterDiffusion.forward, src/models/intergen.py:184-213).  This script
 measures that -- N items (default 16), T uniform in [60, 300], B = 1 per call -- and then the same items through ``sample_many(batching="ragged")`` on the
-SAME model / handle, at the sizes of configs/models/InterGen.yaml / MDM.yaml with synthetic weights.  The motions are asserted bitwise equal; items/s of
+SAME model / handle, at the sizes of configs/models/InterGen.yaml / MDM.yaml / in2IN.yaml with synthetic weights (in2in-dual: both denoisers at in2IN.yaml's
+sizes, W_FUNC "exp" / W_VALUE 0.004 as the dual configuration of the reference's inference script passes them).  The motions are asserted bitwise equal; items/s of
 both and their ratio are printed as one JSON line per model.
 
-    python tools/standalone_eval.py [--model intergen|mdm|both] [--items 16] [--sampler ddim50] [--precision fp32|fp32_split|bf16|bf16_fp8]
+    python tools/standalone_eval.py [--model intergen|mdm|both|in2in-interaction|in2in-dual] [--items 16] [--sampler ddim50] [--precision fp32|fp32_split|bf16|bf16_fp8]
 """
 import argparse
 import json
@@ -31,6 +32,16 @@ def build(name, sampler, precision):
         m.load_state_dict(draw(denoiser_shapes("decoder.net.", cfg.LATENT_DIM, cfg.FF_SIZE, cfg.NUM_LAYERS)))
         m.decoder.precision = precision
         return m, 768, 524
+    if name.startswith("in2in-"):
+        mode = name[len("in2in-"):]
+        cfg = CfgNode(dict(get_config(os.path.join(ROOT, "configs", "models", "in2IN.yaml")), STRATEGY=sampler, W_FUNC="exp", W_VALUE=0.004))
+        m = models.in2IN(cfg, mode)
+        sd = {}
+        for net in (("net_interaction.",) if mode == "interaction" else ("net_individual.", "net_interaction.")):
+            sd.update(draw(denoiser_shapes("decoder." + net, cfg.LATENT_DIM, cfg.FF_SIZE, cfg.NUM_LAYERS)))
+        m.load_state_dict(sd)
+        m.decoder.precision = precision
+        return m, (3 if mode == "interaction" else 5) * 768, 524
     cfg = get_config(os.path.join(ROOT, "configs", "models", "MDM.yaml"))
     m = models.MDM(cfg, num_frames=300, sampling_strategy=sampler)
     sd = draw(mdm_denoiser_shapes("model.", cfg.LATENT_DIM, cfg.FF_SIZE, cfg.NUM_LAYERS))
@@ -50,7 +61,14 @@ def measure(name, args):
     batches = []
     for i, T in enumerate(lens):
         g = torch.Generator().manual_seed(100 + i)
-        batches.append({"cond": torch.randn(1, cw, generator=g).cuda(), "x_T": torch.randn(1, T, width, generator=g).cuda(), "motion_lens": torch.tensor([T])})
+        cond = torch.randn(1, cw, generator=g).cuda()
+        b = {"x_T": torch.randn(1, T, width, generator=g).cuda(), "motion_lens": torch.tensor([T])}
+        if name.startswith("in2in-"):           # the text slices under the names in2INDiffusion.forward concatenates
+            keys = ("cond_interaction", "cond_interaction_individual1", "cond_interaction_individual2", "cond_individual_individual1", "cond_individual_individual2")
+            b.update({k: cond[:, 768 * j:768 * (j + 1)] for j, k in enumerate(keys[:cw // 768])})
+        else:
+            b["cond"] = cond
+        batches.append(b)
 
     def run(fn, warm):
         with torch.no_grad():
@@ -74,7 +92,7 @@ def measure(name, args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", default="both", choices=("intergen", "mdm", "both"))
+    ap.add_argument("--model", default="both", choices=("intergen", "mdm", "both", "in2in-interaction", "in2in-dual"))
     ap.add_argument("--items", type=int, default=16)
     ap.add_argument("--sampler", default="ddim50")
     ap.add_argument("--precision", default="fp32", choices=("fp32", "fp32_split", "bf16", "bf16_fp8"), help="MDM: fp32 or fp32_split")
