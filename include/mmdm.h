@@ -289,6 +289,18 @@ int mmdm_randn_f32(unsigned long long seed, int loop_pos, int B, int T, float* o
 int mmdm_cfg_ddim_f32(const float* m, const float* coef, int S, const int* step_idx, float cfg_scale,
                       float* x, float* pred_xstart, int B, int T, int C, void* stream);
 
+/* The REVERSE update of the single-chain samplers -- DDIM inversion, GaussianDiffusion.ddim_reverse_sample (gaussian_diffusion.py:908-944): the deterministic
+ * ODE taken one step upwards, in place on x [rows, C]:
+ *   eps = (coef[0][i]*x - x0) / coef[1][i];   x = x0*rev[0][i] + rev[1][i]*eps;   i = *step_idx,
+ * x0 [rows, C] = the step's pred_xstart (what the model, under any guidance wrapper, predicts from x at step i: the forward step at i leaves it in the handle's
+ * pred_xstart buffer, mmdm_get_state); coef as in mmdm_cfg_ddim_f32; rev [2, S] fp32 = sqrt(alphas_cumprod_next), sqrt(1 - alphas_cumprod_next) with
+ * alphas_cumprod_next = append(alphas_cumprod[1:], 0) cast to fp32, then fp32 sqrt / 1 - x (:356, :936-942): at i = S - 1 the rows are (0, 1) and x becomes eps.
+ * The same arithmetic as the forward update (one device function), rows 2 / 3 of coef replaced; no noise form (the reference asserts eta == 0).
+ * row_item: NULL, or DEVICE ints [rows] -- a row with row_item[r] < 0 (a padding row of a ragged group) is left untouched.  The step takes x from the level
+ * of alphas_cumprod[i] to that of alphas_cumprod[i + 1].  mixermdm_amd.Sampler.invert drives it: forward step at i for x0, this update, x written back. */
+int mmdm_ddim_reverse_f32(const float* x0, const float* coef, const float* rev, int S, const int* step_idx, float* x, int rows, int C,
+                          const int* row_item, void* stream);
+
 /* Temporal smoothing of generated motions: out[b,t,c] = sum_k w[k+radius] * x[b, clamp(t+k, 0, T-1), c], accumulated in
  * double.  `weights` is a DEVICE array of 2*radius+1 doubles (the normalised gaussian of scipy's _gaussian_kernel1d).
  * Replaces scipy.ndimage.gaussian_filter1d(motion, 1, axis=0, mode='nearest')  src/scripts/infer/mixermdm.py:130. */

@@ -133,6 +133,7 @@ SYMBOLS = {
     "mmdm_begin": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "mmdm_set_eta": (_I, [_VP, _VP, _I]),
     "mmdm_begin_opts": (_I, [_VP, _VP, _VP, _I, _I, C.POINTER(BeginOptions), _VP]),
+    "mmdm_ddim_reverse_f32": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _I, _VP, _VP]),
     "mmdm_randn_f32": (_I, [C.c_ulonglong, _I, _I, _I, _VP, _VP]),
     "mmdm_begin_ragged": (_I, [_VP, _VP, _VP, _I, _VP, _VP]),
     "mmdm_begin_ragged_opts": (_I, [_VP, _VP, _VP, _I, _VP, C.POINTER(BeginRaggedOptions), _VP]),

@@ -717,6 +717,24 @@ __global__ __launch_bounds__(256) void dual_ddim_kernel(const float* __restrict_
     combine_ddim<RAG, NOISE>(DualX0{mi, mI, wtab, s_ind, s_int, per_batch_total}, coef, S, step_idx, x, px, per_batch_total, na...);
 }
 
+// The REVERSE update of the one-chain samplers (GaussianDiffusion.ddim_reverse_sample, gaussian_diffusion.py:932-944): the deterministic ODE taken upwards,
+//   eps = (c_recip[i] x - x0) / c_recipm1[i];   x = x0 sqrt(ab_next[i]) + sqrt(1 - ab_next[i]) eps
+// -- the same ddim() with rows 2 / 3 of the coefficient table replaced by the rows of rev [2, S], so a reverse update rounds as a forward update does.  x0 is
+// the step's pred_xstart as the forward step's combine kernel left it (any guidance wrapper).  No noise forms: the reference asserts eta == 0.  Rows of any
+// width C; RAG: row_item [rows] of the group, padding rows (row_item < 0) are left untouched.
+template <bool RAG>
+__global__ __launch_bounds__(256) void ddim_reverse_kernel(const float* __restrict__ x0, const float* __restrict__ coef, const float* __restrict__ rev, int S,
+                                                            const int* __restrict__ step_idx, float* __restrict__ x, size_t total,
+                                                            const int* __restrict__ row_item, int C) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    if constexpr (RAG) {
+        if (row_item[idx / C] < 0) return;
+    }
+    const int i = *step_idx;
+    x[idx] = ddim(x[idx], x0[idx], coef[i], coef[S + i], rev[i], rev[S + i]);
+}
+
 __global__ void step_dec_kernel(int* step_idx, int* loop_pos) { *step_idx -= 1; *loop_pos += 1; }
 __global__ void set_step_kernel(int* step_idx, int* loop_pos, int s, int l) { *step_idx = s; *loop_pos = l; }
 
@@ -1211,6 +1229,18 @@ extern "C" int mmdm_gather_rows_f32(const float* src, const int* idx, float* dst
     if (n == 0) return MMDM_OK;
     if (!src || !idx || !dst || n < 0 || D <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_gather_rows_f32: bad arguments");
     return mmdm_gather_rows(src, idx, dst, n, D, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mmdm_ddim_reverse_f32(const float* x0, const float* coef, const float* rev, int S, const int* step_idx, float* x, int rows, int C,
+                                    const int* row_item, void* stream) {
+    if (rows == 0) return MMDM_OK;
+    if (!x0 || !coef || !rev || !step_idx || !x || S <= 0 || rows < 0 || C <= 0) return mmdm_set_error(MMDM_ERR_ARG, "mmdm_ddim_reverse_f32: bad arguments");
+    const size_t total = (size_t)rows * C;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (row_item) hipLaunchKernelGGL((ddim_reverse_kernel<true>), grid, block, 0, st, x0, coef, rev, S, step_idx, x, total, row_item, C);
+    else hipLaunchKernelGGL((ddim_reverse_kernel<false>), grid, block, 0, st, x0, coef, rev, S, step_idx, x, total, (const int*)nullptr, C);
+    return mmdm_check_launch(row_item ? "ddim_reverse_rag" : "ddim_reverse");
 }
 
 int mmdm_step_dec(int* step_idx, int* loop_pos, hipStream_t st) {

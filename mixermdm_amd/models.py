@@ -785,12 +785,13 @@ class in2INDiffusion(nn.Module):
             raise ValueError(f"in2INDiffusion: x_T [{B}, {T}, {self.WIDTH}] expected, got {tuple(x_T.shape)}")
         return cond, x_T, B, T
 
-    def forward(self, batch, mask=None, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0):
+    def forward(self, batch, mask=None, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0, start_step=None):
         """mask: None as the reference's forward hard-codes (in2in.py:326, 338, 350; a "mask" entry of the batch is never read), or the
         float [B, T, k] key-padding mask for the loop's model_kwargs -- an explicit argument of this port, mode "individual" only.
-        The other keywords are the loop's (InterDiffusion.forward's rules): modes "interaction" and "dual"."""
+        The other keywords are the loop's (InterDiffusion.forward's rules): modes "interaction" and "dual".  start_step (every mode): x_T is the chain
+        at that respaced step -- the latent of invert(batch, steps=start_step) -- and the loop runs from there (Sampler.sample)."""
         cond, x_T, B, T = self._inputs(batch)
-        loop_kw = dict(eta=eta, seed=seed, step_noise=step_noise, x_start=x_start, init_image=init_image, skip_timesteps=skip_timesteps)
+        loop_kw = dict(eta=eta, seed=seed, step_noise=step_noise, x_start=x_start, init_image=init_image, skip_timesteps=skip_timesteps, start_step=start_step)
         if mask is not None or self.mode == "individual":
             s = self._get_sampler(B, T, legacy=mask is not None)
             with _KeyMask(s, mask):                  # model_kwargs = {"mask": mask, "cond": cond} of the loop
@@ -801,6 +802,16 @@ class in2INDiffusion(nn.Module):
         """InterDiffusion.sample_many for this model: batch dicts as forward takes them, every motion bit-identical to that batch's own forward call.
         Mode "individual" runs ragged without the loop's options (NotImplementedError with the library's message otherwise)."""
         return _StandaloneDiffusion._sample_many(self, batches, batching, max_rows, max_items, eta, skip_timesteps, options=self.mode != "individual")
+
+    def invert(self, batch, steps=None):
+        """DDIM inversion of batch["motions"] [B, T, WIDTH] (normalised space) under the batch's cond_* entries -> {"latent": [B, T, WIDTH], "steps": k}: the
+        chain at respaced step k (None = all S steps: the x_T of a plain forward).  For k < S, forward(dict(batch, x_T=latent), start_step=k) walks the
+        same levels down again."""
+        return _invert(self, batch, steps)
+
+    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
+        """invert for many batches with sample_many's packing: every latent bit-identical to that batch's own invert call."""
+        return _invert_many(self, batches, batching, steps, max_rows, max_items)
 
 
 class in2IN(nn.Module):
@@ -883,6 +894,18 @@ class in2IN(nn.Module):
             batches = [self._text_all(dict(b)) for b in batches]
         return self.decoder.sample_many(batches, batching=batching, max_rows=max_rows, max_items=max_items, eta=eta, skip_timesteps=skip_timesteps)
 
+    def invert(self, batch, steps=None):
+        """in2INDiffusion.invert after forward_test's text stage."""
+        with torch.no_grad():
+            batch = self._text_all(dict(batch))
+        return self.decoder.invert(batch, steps)
+
+    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
+        """in2INDiffusion.invert_many after forward_test's text stage."""
+        with torch.no_grad():
+            batches = [self._text_all(dict(b)) for b in batches]
+        return self.decoder.invert_many(batches, batching=batching, steps=steps, max_rows=max_rows, max_items=max_items)
+
 
 # ---- stand-alone InterGen and MDM samplers ---------------------------------------------------------------------------------------
 def _unwrap_checkpoint(state_dict):
@@ -927,7 +950,7 @@ def _loop_forms(batches, eta, who):
     return form, seeds
 
 
-def _loop_call(s, cond, x_T, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0):
+def _loop_call(s, cond, x_T, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0, start_step=None):
     """One sampling call with the loop's other arguments on a sampler that takes them (single_only 0 / 4).  eta > 0 needs its step noise: step_noise
     [>= S - skip, B, T, 524] or seed (the device generator; with neither, a seed is drawn from torch's default generator).  eta belongs to the call."""
     eta = float(eta)
@@ -943,8 +966,10 @@ def _loop_call(s, cond, x_T, eta=0.0, seed=None, step_noise=None, x_start=None, 
     if not 0 <= skip < S:
         raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
     try:
-        return s.sample(cond, x_T, eta=eta, noise=step_noise[:S - skip] if step_noise is not None else None, seed=seed, x_start=x_start,
-                        init_image=init_image, skip_timesteps=skip)
+        kw = dict(eta=eta, noise=step_noise[:S - skip] if step_noise is not None else None, seed=seed, x_start=x_start, init_image=init_image, skip_timesteps=skip)
+        if start_step is not None:
+            return s.sample_from(cond, x_T, start_step, **kw)
+        return s.sample(cond, x_T, **kw)
     finally:
         if eta:
             s.set_eta(0.0)
@@ -958,7 +983,64 @@ def _refusable_loop_call(s, cond, x_T, loop_kw):
         kw["noise"] = kw.pop("step_noise")
     if kw.get("eta") and "noise" not in kw and "seed" not in kw:
         kw["seed"] = 0
+    if "start_step" in kw:
+        return _unsupported(s.sample_from, cond, x_T, kw.pop("start_step"), **kw)
     return _unsupported(s.sample, cond, x_T, **kw)
+
+
+def pack_groups(Bs, Ts, max_rows=4800, max_items=64):
+    """The packing rule of sample_many / invert_many: the motions (batch i, row j) in batch order, cut into ragged groups of <= max_rows frames and
+    <= max_items motions (a motion longer than max_rows is a group of its own).  -> list of groups, each a list of (i, j)."""
+    groups, cur, rows = [], [], 0
+    for i, nb in enumerate(Bs):
+        for j in range(nb):
+            if cur and (rows + Ts[i] > max_rows or len(cur) >= max_items):
+                groups.append(cur)
+                cur, rows = [], 0
+            cur.append((i, j))
+            rows += Ts[i]
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def _invert_inputs(model, batch):
+    """(cond, x_0, B, T) of an inversion call: the model's cond entries and batch["motions"] [B, T, WIDTH]."""
+    if batch.get("motions") is None:
+        raise ValueError(f"{type(model).__name__}.invert: the batch gives no 'motions' [B, T, {model.WIDTH}]")
+    m = batch["motions"]
+    if m.dim() != 3:
+        raise ValueError(f"{type(model).__name__}.invert: motions [B, T, {model.WIDTH}] expected, got {tuple(m.shape)}")
+    return model._inputs(dict(batch, x_T=m, motion_lens=[m.shape[1]]))
+
+
+def _invert(model, batch, steps):
+    from .sampler import invert_steps
+    cond, x_0, B, T = _invert_inputs(model, batch)
+    s = model._get_sampler(B, T)
+    k = invert_steps(steps, s.schedule.num_timesteps)
+    return {"latent": _unsupported(s.invert, cond, x_0, k), "steps": k}
+
+
+def _invert_many(model, batches, batching, steps, max_rows, max_items):
+    from .sampler import invert_steps
+    who = f"{type(model).__name__}.invert_many"
+    if batching not in ("sequential", "ragged"):
+        raise ValueError(f'{who}: batching {batching!r} not recognized ("ragged" or "sequential")')
+    if batching == "sequential":
+        return [_invert(model, b, steps) for b in batches]
+    ins = [_invert_inputs(model, b) for b in batches]
+    Bs, Ts = [v[2] for v in ins], [v[3] for v in ins]
+    groups = pack_groups(Bs, Ts, max_rows, max_items)
+    Tm = max(max(Ts), model.num_frames)
+    smp = model._get_sampler(max(max(len(g) for g in groups), -(-max(sum(Ts[i] for i, _ in g) for g in groups) // Tm)), Tm)
+    k = invert_steps(steps, smp.schedule.num_timesteps)
+    outs = [[None] * nb for nb in Bs]
+    for g in groups:
+        items = _unsupported(smp.invert_ragged, torch.cat([ins[i][0][j:j + 1] for i, j in g], 0), [ins[i][1][j] for i, j in g], [Ts[i] for i, _ in g], k)
+        for (i, j), it in zip(g, items):
+            outs[i][j] = it
+    return [{"latent": torch.stack(o, 0), "steps": k} for o in outs]
 
 
 class _StandaloneDiffusion(nn.Module):
@@ -1086,6 +1168,17 @@ class _StandaloneDiffusion(nn.Module):
         return [{"output": torch.stack(o, 0)} for o in outs]
 
 
+    def invert(self, batch, steps=None):
+        """DDIM inversion of batch["motions"] [B, T, WIDTH] (normalised space) under batch["cond"] -> {"latent": [B, T, WIDTH], "steps": k}: the chain at
+        respaced step k (None = all S steps: the x_T of a plain forward).  For k < S, forward(dict(batch, x_T=latent), start_step=k) walks the same levels
+        down again."""
+        return _invert(self, batch, steps)
+
+    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
+        """invert for many batches with sample_many's packing: every latent bit-identical to that batch's own invert call."""
+        return _invert_many(self, batches, batching, steps, max_rows, max_items)
+
+
 class InterDiffusion(_StandaloneDiffusion):
     """InterDiffusion (src/models/intergen.py:96-213): InterDenoiser ``net`` under ClassifierFreeSampleModel(cfg.CFG_WEIGHT) in the single-chain DDIM loop,
     [B, T, 524] in the model's normalised space.  Runs on ``Sampler(single_only=4, model2_kind=1)``; ``.precision`` picks the handle's mode (all four).
@@ -1119,12 +1212,12 @@ class InterDiffusion(_StandaloneDiffusion):
     def _sampler_state(self):
         return {"denoiser2." + k[len("net."):]: p.data for k, p in self.named_parameters()}
 
-    def forward(self, batch, *, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0):
+    def forward(self, batch, *, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0, start_step=None):
         """intergen.py:184-213 -> {"output": [B, T, 524]}.  eta > 0 needs its step noise: step_noise [>= S - skip, B, T, 524] or seed (the device generator;
-        with neither, a seed is drawn from torch's default generator)."""
+        with neither, a seed is drawn from torch's default generator).  start_step: x_T is the chain at that respaced step (Sampler.sample)."""
         cond, x_T, B, T = self._inputs(batch)
         return {"output": _loop_call(self._get_sampler(B, T), cond, x_T, eta=eta, seed=seed, step_noise=step_noise, x_start=x_start, init_image=init_image,
-                                     skip_timesteps=skip_timesteps)}
+                                     skip_timesteps=skip_timesteps, start_step=start_step)}
 
     def sample_many(self, batches, batching="ragged", max_rows=4800, max_items=64, *, eta=0.0, skip_timesteps=0):
         """Many forward calls at once (batch dicts with 'cond' [b, 768], 'motion_lens', optionally 'x_T' [b, T, 524]) -> one {"output"} per batch, every
@@ -1201,6 +1294,18 @@ class InterGen(nn.Module):
         batch = self.text_process(batch)
         batch.update(self.decoder(batch, **loop_kw))
         return batch
+
+    def invert(self, batch, steps=None):
+        """InterDiffusion.invert after text_process."""
+        with torch.no_grad():
+            batch = self.text_process(dict(batch))
+        return self.decoder.invert(batch, steps)
+
+    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
+        """InterDiffusion.invert_many after text_process."""
+        with torch.no_grad():
+            batches = [self.text_process(dict(b)) for b in batches]
+        return self.decoder.invert_many(batches, batching=batching, steps=steps, max_rows=max_rows, max_items=max_items)
 
     def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
         """InterDiffusion.sample_many after text_process; mode / inflight / keep_history are accepted for generate_for_evaluation's call and unused (one chain,
@@ -1284,6 +1389,20 @@ class MDM(_StandaloneDiffusion):
 
     def forward_test(self, batch):
         return self.forward(batch)
+
+    def _with_cond(self, batch):
+        b = dict(batch)
+        with torch.no_grad():
+            b["cond"] = self.generate_cond(b)
+        return b
+
+    def invert(self, batch, steps=None):
+        """DDIM inversion of batch["motions"] [B, T, 262] under the batch's text / 'cond' -> {"latent": [B, T, 262], "steps": k}."""
+        return _invert(self, self._with_cond(batch), steps)
+
+    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
+        """invert for many batches over the ragged path of the single-person sampler (its token-row maps), bit-identical to the sequential calls."""
+        return _invert_many(self, [self._with_cond(b) for b in batches], batching, steps, max_rows, max_items)
 
     def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
         """Many forward calls at once over the ragged path of the single-person sampler -> one {"output": [b, T, 262]} per batch, bit-identical to the

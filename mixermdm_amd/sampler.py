@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Config, BeginOptions, BeginRaggedOptions, load_library, check
+from ._lib import Config, BeginOptions, BeginRaggedOptions, MMDMError, load_library, check
 from .schedule import make_schedule
 
 STATS_ORDER = ("mean_hml", "std_hml", "mean_ih", "std_ih")
@@ -97,6 +97,26 @@ def pack_ragged_options(lens, *, noise=None, seeds=None, noise_rows=None, x_star
             raise ValueError(f"ragged options: init_image [{total}, 524] expected, got {tuple(init_image.shape)}")
         init_image = init_image.contiguous()
     return dict(noise=noise, seeds=seeds, noise_rows=noise_rows, x_start=x_start, init_image=init_image, skip_timesteps=int(skip_timesteps))
+
+
+def invert_steps(steps, S):
+    """The number of reverse steps an inversion runs: None = all S; otherwise an int in [1, S] (ValueError)."""
+    if steps is None:
+        return int(S)
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= int(steps) <= S:
+        raise ValueError(f"invert: steps={steps!r} outside [1, {S}] (None = all {S} steps of the schedule)")
+    return int(steps)
+
+
+def check_start_step(start_step, S, *, init_image=None, skip_timesteps=0):
+    """start_step of sample_from / sample_ragged_from: the respaced step index in [0, S) whose level x_T is taken at -- the loop then runs start_step + 1
+    steps (a partial inversion of k < S steps continues with start_step = k).  It is exclusive with init_image / skip_timesteps, which name the loop's first
+    step themselves (ValueError)."""
+    if isinstance(start_step, bool) or not isinstance(start_step, (int, np.integer)) or not 0 <= int(start_step) < S:
+        raise ValueError(f"start_step={start_step!r} outside [0, {S})")
+    if init_image is not None or skip_timesteps:
+        raise ValueError("start_step is exclusive with init_image / skip_timesteps: both name the first step of the loop")
+    return int(start_step)
 
 
 class Sampler:
@@ -270,11 +290,13 @@ class Sampler:
         with torch.cuda.device(self.device):
             if valid is None:
                 check(self.lib.mmdm_set_key_mask(self.h, None, 0, 0), self.h)
+                self._reverse_mask = False
                 return self
             v = np.ascontiguousarray((torch.as_tensor(valid).detach().cpu().numpy() != 0).astype(np.uint8))
             if v.ndim != 2:
                 raise ValueError(f"set_key_mask: [rows, T] expected, got {v.shape}")
             check(self.lib.mmdm_set_key_mask(self.h, v.ctypes.data_as(C.c_void_p), v.shape[0], v.shape[1]), self.h)
+        self._reverse_mask = True                # (begin_reverse refuses a masked handle by name)
         return self
 
     # ---- sampling ---------------------------------------------------------------------------------
@@ -399,6 +421,133 @@ class Sampler:
         self._hist = None
         self._left = self._steps = S - skip
         return self
+
+    # ---- DDIM inversion (one-chain samplers) ------------------------------------------------------------
+    def _reverse_refusals(self, who):
+        """The sampler modes an inversion covers, refused by name otherwise with the status of MMDM_ERR_UNSUPPORTED / MMDM_ERR_STATE."""
+        so = self.single_only
+        if so == 0:
+            raise MMDMError(f"[mmdm status 4] {who}: the two-chain MixerMDM sampler (single_only = 0) has no reverse step: MixerDiffusion overrides the step "
+                            "and the reference gives it no reverse form", 4)
+        if so in (2, 3):
+            raise MMDMError(f"[mmdm status 4] {who}: single_only = {so} is superseded by single_only = 4 with cfg_form = {so - 1}, which takes the reverse step", 4)
+        if getattr(self, "_reverse_mask", False):
+            raise MMDMError(f"[mmdm status 4] {who}: a key mask is set on the handle; the reverse step takes none (clear it with set_key_mask(None))", 4)
+        if getattr(self, "eta", 0.0):
+            raise MMDMError(f"[mmdm status 2] {who}: eta is set on the handle; the reverse ODE is the deterministic path only (set_eta(0) clears it)", 2)
+
+    def _reverse_start(self, lens):
+        """Takes over the begun forward call: the motion is in the handle's x; the tables and the row map of the reverse update go to the device."""
+        sch = self.schedule
+        key = (sch.key(), str(self.device))
+        if getattr(self, "_rev_key", None) != key:
+            self._rev_coef = torch.from_numpy(np.ascontiguousarray(sch.device_coefficients())).to(self.device)
+            self._rev_tab = torch.from_numpy(np.ascontiguousarray(sch.reverse_coefficients())).to(self.device)
+            self._rev_idx = torch.arange(sch.num_timesteps, dtype=torch.int32, device=self.device)
+            self._rev_key = key
+        item = None
+        if lens is not None:                     # frame row -> item, -1 for the group's padding rows (they stay zero)
+            m = np.full(self.rows, -1, dtype=np.int32)
+            m[:sum(lens)] = np.repeat(np.arange(len(lens), dtype=np.int32), lens)
+            item = torch.from_numpy(m).to(self.device)
+        st = self.state(sync=False)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            self._rev_x = st["x"].clone()
+        for t in (self._rev_coef, self._rev_tab, self._rev_idx, item):
+            if t is not None:
+                t.record_stream(self.stream)
+        self._rev_item, self._rev_pos = item, 0
+        return self
+
+    def begin_reverse(self, cond, x_0):
+        """Begin a DDIM inversion of the motion x_0 [B, T, C] (GaussianDiffusion.ddim_reverse_sample, gaussian_diffusion.py:908-944; the one-chain samplers:
+        single_only 1 / 4).  run_reverse() then takes reverse steps from respaced step 0 upwards; state()["x"] is the latent, state()["pred_xstart"] the
+        last step's x0."""
+        self._reverse_refusals("begin_reverse")
+        self.begin(cond, x_0)
+        return self._reverse_start(None)
+
+    def begin_reverse_ragged(self, cond, x_0, lens):
+        """begin_reverse for B motions of different lengths (begin_ragged's layout).  Every item's latent is bit-identical to inverting it alone."""
+        self._reverse_refusals("begin_reverse_ragged")
+        self.begin_ragged(cond, x_0, lens)
+        return self._reverse_start(self.lens)
+
+    def run_reverse(self, nsteps=None, use_graph=True):
+        """nsteps reverse steps (None: those that are left, S - position).  The step at respaced index i: the forward step at i on the handle gives the model's
+        x0 under the guidance wrapper (pred_xstart; its own update of x is discarded), mmdm_ddim_reverse_f32 takes x from the level of alphas_cumprod[i] to
+        that of alphas_cumprod[i + 1], and x is written back.  Everything is queued on the sampler's stream; no host synchronisation."""
+        if getattr(self, "_rev_x", None) is None:
+            raise MMDMError("[mmdm status 2] run_reverse: call begin_reverse / begin_reverse_ragged first", 2)
+        S, i0 = self.schedule.num_timesteps, self._rev_pos
+        n = S - i0 if nsteps is None else int(nsteps)
+        if n < 0 or n > S - i0:
+            raise MMDMError(f"[mmdm status 1] run_reverse: {n} reverse steps requested, {S - i0} left in the schedule", 1)
+        x = self._rev_x
+        C_ = x.shape[-1]
+        rows = x.numel() // C_
+        for i in range(i0, i0 + n):
+            self.seek(i)
+            self.run(1, use_graph)
+            st = self.state(sync=False)
+            with torch.cuda.device(self.device):
+                check(self.lib.mmdm_ddim_reverse_f32(C.c_void_p(st["pred_xstart"].data_ptr()), C.c_void_p(self._rev_coef.data_ptr()),
+                                                     C.c_void_p(self._rev_tab.data_ptr()), S, C.c_void_p(self._rev_idx.data_ptr() + 4 * i),
+                                                     C.c_void_p(x.data_ptr()), rows, C_,
+                                                     C.c_void_p(self._rev_item.data_ptr()) if self._rev_item is not None else None, self._s()))
+            with torch.cuda.stream(self.stream):
+                st["x"].copy_(x)
+        self._rev_pos = i0 + n
+        return self
+
+    def invert(self, cond, x_0, steps=None, use_graph=True):
+        """DDIM inversion (ddim_reverse_sample driven `for i in range(steps)`, clip_denoised=False): the latent [B, T, C] at the level of respaced step
+        `steps` (None = S: the ab_next = 0 level, the x_T of a plain sample).  For steps = k < S, sample_from(cond, latent, k) walks the same levels down
+        again and ends the loop."""
+        k = invert_steps(steps, self.schedule.num_timesteps)
+        self.begin_reverse(cond, x_0)
+        self.run_reverse(k, use_graph)
+        lat = self.state()["x"].clone()
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return lat
+
+    def invert_ragged(self, cond, x_0, lens, steps=None, use_graph=True):
+        """invert for a ragged batch: list of B latents [T_i, C], each bit-identical to invert(cond[b:b+1], x_b[None], steps)[0]."""
+        k = invert_steps(steps, self.schedule.num_timesteps)
+        self.begin_reverse_ragged(cond, x_0, lens)
+        self.run_reverse(k, use_graph)
+        lat = self.state()["x"][:sum(self.lens)].clone()
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return [lat[o:o + t] for o, t in self.item_slices()]
+
+    def sample_from(self, cond, x_k, start_step, use_graph=True, *, eta=None, **opts):
+        """sample() of a chain that stands at respaced step `start_step`: x_k is its state there (a partial inversion: invert(steps=start_step)) and the loop
+        runs the start_step + 1 steps start_step .. 0 -- begin followed by seek.  start_step = S - 1 is sample().  eta and the keywords are sample()'s;
+        init_image / skip_timesteps are refused (they name the first step themselves)."""
+        k = check_start_step(start_step, self.schedule.num_timesteps, init_image=opts.get("init_image"), skip_timesteps=opts.get("skip_timesteps", 0))
+        if eta is not None and float(eta) != getattr(self, "eta", 0.0):
+            self.set_eta(eta)
+        self.begin(cond, x_k, **opts)
+        self.seek(k)
+        self.run(None, use_graph)
+        st = self.state()
+        res = st["pred_xstart"] if self.single_only else st["pred_xstart2"]
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return res.clone()
+
+    def sample_ragged_from(self, cond, x_k, lens, start_step, use_graph=True, *, eta=None, **opts):
+        """sample_from for a ragged batch: list of B results [T_i, C]."""
+        k = check_start_step(start_step, self.schedule.num_timesteps, init_image=opts.get("init_image"), skip_timesteps=opts.get("skip_timesteps", 0))
+        if eta is not None and float(eta) != getattr(self, "eta", 0.0):
+            self.set_eta(eta)
+        self.begin_ragged(cond, x_k, lens, **opts)
+        self.seek(k)
+        self.run(None, use_graph)
+        st = self.state()
+        res = (st["pred_xstart"] if self.single_only else st["pred_xstart2"])[:sum(self.lens)].clone()
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return [res[o:o + t] for o, t in self.item_slices()]
 
     def item_slices(self):
         """(first row, length) of every item inside a group of a ragged call's buffers."""

@@ -118,6 +118,14 @@ class RespacedSchedule:
         sigma = np.float32(eta) * np.sqrt((one - ab_prev) / (one - ab)) * np.sqrt(one - ab / ab_prev)
         return np.stack([np.sqrt(one - ab_prev - sigma * sigma), sigma]).astype(np.float32)
 
+    def reverse_coefficients(self):
+        """[2, S] fp32: sqrt(ab_next), sqrt(1 - ab_next) of the DDIM reverse ODE (ddim_reverse_sample, gaussian_diffusion.py:936-942), in the
+        reference's fp32 operation order: alphas_cumprod_next = append(alphas_cumprod[1:], 0.0) (:356) as a float64 table, cast to fp32 by
+        _extract_into_tensor, then th.sqrt and 1 - x in fp32.  At i = S - 1 the rows are (0, 1): the last reverse step leaves eps."""
+        ab_next = np.append(self.alphas_cumprod[1:], 0.0).astype(np.float32)
+        one = np.float32(1.0)
+        return np.stack([np.sqrt(ab_next), np.sqrt(one - ab_next)]).astype(np.float32)
+
     def q_sample_coefficients(self, i):
         """(sqrt_alphas_cumprod[i], sqrt_one_minus_alphas_cumprod[i]) as q_sample reads them: float64 tables (gaussian_diffusion.py:354-355)
         cast to fp32 by _extract_into_tensor."""

@@ -7,7 +7,11 @@ SAME model / handle, at the sizes of configs/models/InterGen.yaml / MDM.yaml / i
 sizes, W_FUNC "exp" / W_VALUE 0.004 as the dual configuration of the reference's inference script passes them).  The motions are asserted bitwise equal; items/s of
 both and their ratio are printed as one JSON line per model.
 
+--invert measures DDIM inversion the same way: every item carries a motion instead of x_T, the per-item ``invert`` loop is compared with
+``invert_many(batching="ragged")``, the latents are asserted bitwise equal.
+
     python tools/standalone_eval.py [--model intergen|mdm|both|in2in-interaction|in2in-dual] [--items 16] [--sampler ddim50] [--precision fp32|fp32_split|bf16|bf16_fp8]
+                                    [--invert]
 """
 import argparse
 import json
@@ -63,6 +67,8 @@ def measure(name, args):
         g = torch.Generator().manual_seed(100 + i)
         cond = torch.randn(1, cw, generator=g).cuda()
         b = {"x_T": torch.randn(1, T, width, generator=g).cuda(), "motion_lens": torch.tensor([T])}
+        if args.invert:                         # a motion in the models' normalised space instead of the start noise
+            b = {"motions": 0.5 * b["x_T"]}
         if name.startswith("in2in-"):           # the text slices under the names in2INDiffusion.forward concatenates
             keys = ("cond_interaction", "cond_interaction_individual1", "cond_interaction_individual2", "cond_individual_individual1", "cond_individual_individual2")
             b.update({k: cond[:, 768 * j:768 * (j + 1)] for j, k in enumerate(keys[:cw // 768])})
@@ -78,15 +84,20 @@ def measure(name, args):
             res = fn(batches)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-        return [r["output"] for r in res], dt
+        return [r["latent" if args.invert else "output"] for r in res], dt
 
-    ref, t_seq = run(lambda b: [model.forward_test(dict(x)) for x in b], 3)
-    got, t_rag = run(lambda b: model.sample_many([dict(x) for x in b], batching="ragged", max_rows=args.max_rows), N)
+    if args.invert:
+        ref, t_seq = run(lambda b: [model.invert(dict(x)) for x in b], 3)
+        got, t_rag = run(lambda b: model.invert_many([dict(x) for x in b], batching="ragged", max_rows=args.max_rows), N)
+    else:
+        ref, t_seq = run(lambda b: [model.forward_test(dict(x)) for x in b], 3)
+        got, t_rag = run(lambda b: model.sample_many([dict(x) for x in b], batching="ragged", max_rows=args.max_rows), N)
     same = all(torch.equal(a, b) for a, b in zip(ref, got))
     assert same, "ragged batches and the per-item loop differ"
     assert all(torch.isfinite(o).all().item() for o in got)
-    print(json.dumps({"metric": "items/s, stand-alone %s (one forward_test per item, B = 1, %s, T uniform in [60, 300])" % (name, args.sampler), "items": N,
-                      "frames": sum(lens), "precision": args.precision, "sequential_forward_test": {"wall_s": round(t_seq, 3), "items_per_s": round(N / t_seq, 4)},
+    what = "one invert per item" if args.invert else "one forward_test per item"
+    print(json.dumps({"metric": "items/s, stand-alone %s (%s, B = 1, %s, T uniform in [60, 300])" % (name, what, args.sampler), "items": N,
+                      "frames": sum(lens), "precision": args.precision, "sequential_invert" if args.invert else "sequential_forward_test": {"wall_s": round(t_seq, 3), "items_per_s": round(N / t_seq, 4)},
                       "ragged": {"wall_s": round(t_rag, 3), "items_per_s": round(N / t_rag, 4)}, "ratio": round(t_seq / t_rag, 3), "bit_identical": bool(same)}), flush=True)
 
 
@@ -97,6 +108,7 @@ def main():
     ap.add_argument("--sampler", default="ddim50")
     ap.add_argument("--precision", default="fp32", choices=("fp32", "fp32_split", "bf16", "bf16_fp8"), help="MDM: fp32 or fp32_split")
     ap.add_argument("--max-rows", type=int, default=4800, help="frames per ragged batch (16 x 300)")
+    ap.add_argument("--invert", action="store_true", help="DDIM inversion: the per-item invert loop against invert_many(batching=\"ragged\")")
     args = ap.parse_args()
     for name in (("intergen", "mdm") if args.model == "both" else (args.model,)):
         measure(name, args)
