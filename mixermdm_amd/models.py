@@ -186,7 +186,7 @@ class MixerDiffusion:
         if eta == 0.0:
             step_noise = seed = None
         elif step_noise is None and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seed = _draw_seed()
         opts = dict(eta=eta, noise=step_noise, seed=seed, x_start=x_start, init_image=init_image, skip_timesteps=int(skip_timesteps))
         mixer = model.model if isinstance(model, ClassifierFreeSampleModelX2) else model
         owner = mixer._owner
@@ -197,6 +197,21 @@ class MixerDiffusion:
         dev = owner.device
         x_T = noise if noise is not None else torch.randn(*shape, device=dev)
         return owner._run_loop(self, cond, x_T, cfg_scale=getattr(model, "s", owner.cfg_mixing_weight), mask=mask, opts=opts)
+
+
+def _history_plan(mode, store_influence, keep_history, S, skip, history_every, mixing_mode):
+    """The history side outputs of a MixerMDM call -> ({name: width} in the library's order, slots, bytes per (motion, frame)).  keep_history: None = what
+    the mode says (store_influence -> the influences; "eval" -> out1 / out2 / out_influenced), False = none.  One slot per EXECUTED step, every
+    history_every-th; modes 1-2 keep the un-expanded [2B, T, 1] influence (mixermdm.py:739-745); a frame has a cond and an uncond row of fp32."""
+    names = []
+    if keep_history is None or keep_history:
+        if store_influence:
+            names += ["influence_i1", "influence_i2"]
+        if mode == "eval":
+            names += ["out1", "out2", "out_influenced"]
+    kept = {n: (262 if mixing_mode >= 3 else 1) if n.startswith("influence") else 524 for n in names}
+    slots = (S - skip + history_every - 1) // history_every
+    return kept, slots, slots * 2 * 4 * sum(kept.values())
 
 
 class MixerMDM(nn.Module):
@@ -398,15 +413,7 @@ class MixerMDM(nn.Module):
         # the facade builds a new MixerDiffusion per call (as the reference does, mixermdm.py:515-522): compare schedules by CONTENT so
         # that the tables are uploaded, the time-embedding tables rebuilt and (through the (B, T, S) graph cache) nothing re-captured
         # only when the strategy really changed
-        if getattr(smp, "_strategy", None) != sch.key():
-            import ctypes as C
-            from ._lib import check
-            tmap = np.ascontiguousarray(np.array(sch.timestep_map, dtype=np.int32))
-            coef = np.ascontiguousarray(sch.device_coefficients())
-            with torch.cuda.device(smp.device):
-                check(smp.lib.mmdm_set_schedule(smp.h, tmap.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p), sch.num_timesteps, smp._s()), smp.h)
-            smp.schedule, smp._strategy = sch, sch.key()
-            smp.eta = 0.0                                  # mmdm_set_schedule resets the eta table
+        smp.use_schedule(sch)
         opts = dict(opts or {})
         eta = opts.pop("eta", 0.0)
         if eta != getattr(smp, "eta", 0.0):
@@ -415,14 +422,9 @@ class MixerMDM(nn.Module):
         if not 0 <= skip < sch.num_timesteps:
             raise ValueError(f"skip_timesteps={skip} outside [0, {sch.num_timesteps})")
         m = self.mixing
-        names = []
-        if m.store_influence:
-            names += ["influence_i1", "influence_i2"]
-        if m.mode == "eval":
-            names += ["out1", "out2", "out_influenced"]
-        slots = (sch.num_timesteps - skip + self.history_every - 1) // self.history_every      # one entry per EXECUTED step
-        wi = 262 if m.mixing_mode >= 3 else 1          # modes 1-2 keep the un-expanded [2B, T, 1] influence (mixermdm.py:739-745)
-        need = slots * 2 * B * T * 4 * sum(wi if n.startswith("influence") else 524 for n in names)
+        kept, _, per_row = _history_plan(m.mode, m.store_influence, None, sch.num_timesteps, skip, self.history_every, m.mixing_mode)
+        names = list(kept)
+        need = per_row * B * T
         if need > HISTORY_BUDGET_BYTES:
             raise MemoryError(f"history side outputs need {need / 2**30:.1f} GiB for {sch.num_timesteps} steps (the reference keeps every step: "
                               "mixermdm.py:794-808); set model.history_every = k to keep every k-th step, or store_influence=False / forward_test")
@@ -441,17 +443,6 @@ class MixerMDM(nn.Module):
         return out
 
     # ---- many calls at once: the reference's callers, redesigned --------------------------------------------------
-    def _set_schedule_on(self, smp, sch):
-        if getattr(smp, "_strategy", None) != sch.key():
-            import ctypes as C
-            from ._lib import check
-            tmap = np.ascontiguousarray(np.array(sch.timestep_map, dtype=np.int32))
-            coef = np.ascontiguousarray(sch.device_coefficients())
-            with torch.cuda.device(smp.device):
-                check(smp.lib.mmdm_set_schedule(smp.h, tmap.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p), sch.num_timesteps, smp._s()), smp.h)
-            smp.schedule, smp._strategy = sch, sch.key()
-            smp.eta = 0.0
-
     def _pool(self, k, B, T):
         """k samplers over ONE weight set: the facade's own handle plus k - 1 handles that borrow its weights (mmdm_create_shared), each with its
         own stream, workspace (B, T), schedule tables and graph cache."""
@@ -493,34 +484,10 @@ class MixerMDM(nn.Module):
         eta, skip = float(eta), int(skip_timesteps)
         if eta < 0:
             raise ValueError(f"eta={eta} must be >= 0")
-        has = lambda k: [b.get(k) is not None for b in batches]
-        for k in ("x_start", "init_image"):
-            if any(has(k)) and not all(has(k)):
-                raise ValueError(f"sample_many: batch {has(k).index(not has(k)[0])} differs from batch 0 in whether it gives {k!r}: give it for every batch or for none")
-        use_opts = bool(eta or skip or any(has("x_start")) or any(has("init_image")))
-        if use_opts and batching == "inflight":
-            raise ValueError('sample_many: batching="inflight" takes no eta / skip_timesteps / x_start / init_image; use "ragged" or "sequential"')
-        form = None                                       # "seed" | "noise" at eta > 0
-        seeds = [None] * len(batches)
-        if eta:
-            for i, b in enumerate(batches):
-                sd, sn = b.get("seed"), b.get("step_noise")
-                if sd is not None and sn is not None:
-                    raise ValueError(f"sample_many: batch {i} gives both 'seed' and 'step_noise'")
-                f = "noise" if sn is not None else "seed"
-                if form is not None and f != form:
-                    raise ValueError(f"sample_many: batch {i} names its step noise as a {f!r}, batch 0 as a {form!r}: one noise form per call")
-                form = f
-                if f == "seed":                           # as ddim_sample_loop: an un-named seed comes from torch's default generator
-                    seeds[i] = int(sd) if sd is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        use_opts, form, seeds = _loop_forms(batches, eta, skip, "sample_many", no_opts='batching="inflight" takes no eta / skip_timesteps / x_start / init_image; '
+                                            'use "ragged" or "sequential"' if batching == "inflight" else None)
         m = self.mixing
         m.mode = mode
-        names = []
-        if keep_history is None or keep_history:
-            if m.store_influence:
-                names += ["influence_i1", "influence_i2"]
-            if mode == "eval":
-                names += ["out1", "out2", "out_influenced"]
         with torch.no_grad():
             conds = [self.generate_cond(b) for b in batches]
         Ts = [int(b["motion_lens"][0]) for b in batches]
@@ -530,7 +497,8 @@ class MixerMDM(nn.Module):
         sch = MixerDiffusion(use_timesteps=space_timesteps(self.diffusion_steps, self.sampling_strategy), betas=self.betas).schedule
         if not 0 <= skip < sch.num_timesteps:
             raise ValueError(f"skip_timesteps={skip} outside [0, {sch.num_timesteps})")
-        slots = (sch.num_timesteps - skip + self.history_every - 1) // self.history_every      # one entry per EXECUTED step
+        kept, slots, per_row = _history_plan(mode, m.store_influence, keep_history, sch.num_timesteps, skip, self.history_every, m.mixing_mode)
+        names = list(kept)
         keys = ("influence_i1", "influence_i2") + (("out1", "out2", "out_influenced") if mode == "eval" else ())
         results = [{"output": None, **{k: [] for k in keys}} for _ in batches]
         if batching == "sequential":
@@ -555,15 +523,13 @@ class MixerMDM(nn.Module):
         if batching == "inflight":
             pool = self._pool(max(1, int(inflight)), max(Bs), max(Ts))
             for smp in pool:
-                self._set_schedule_on(smp, sch)
+                smp.use_schedule(sch)
             # ONE host thread drives every handle (calls dealt round-robin, nothing synchronised in between).  One thread per handle was built
             # and measured (tools/inflight_probe.py: 4 handles 3.65 vs 4.27 ms per item-step) and is not used: graph launches from two host
             # threads crash inside this runtime's hipGraphLaunch (hip::Graph::UpdateStreams) as soon as the threads also capture new shapes,
             # whatever the locking around captures (LAB_NOTES.md, round 5).  Buffers are allocated up front; the calls are C-ABI calls only.
             conds = [c.to(dev, torch.float32).contiguous() for c in conds]
             xs = [x.contiguous() for x in xs]
-            wi = 262 if m.mixing_mode >= 3 else 1
-            per_row = slots * 2 * 4 * sum(wi if n.startswith("influence") else 524 for n in names)      # history bytes per (motion, frame)
             need = per_row * sum(nb * T for nb, T in zip(Bs, Ts))
             # the history side outputs of EVERY call are the caller's to keep (as in the sequential and ragged paths): the same budget, summed
             if need > HISTORY_BUDGET_BYTES:
@@ -576,7 +542,7 @@ class MixerMDM(nn.Module):
             for w0 in range(0, len(conds), win):
                 idx = range(w0, min(w0 + win, len(conds)))
                 outs = {i: torch.empty_like(xs[i]) for i in idx}
-                hists = {i: {nm: torch.empty(slots, 2 * Bs[i], Ts[i], (wi if nm.startswith("influence") else 524), device=dev) for nm in names} for i in idx}
+                hists = {i: {nm: torch.empty(slots, 2 * Bs[i], Ts[i], width, device=dev) for nm, width in kept.items()} for i in idx}
                 for smp in pool:                     # inputs and buffers were produced on the caller's stream: order every handle's stream behind it
                     smp.stream.wait_stream(cur)
                 for i in idx:
@@ -590,69 +556,21 @@ class MixerMDM(nn.Module):
                         results[i][k] = list(v.unbind(0))
             return results
         # ragged: motions in call order, cut into groups of <= max_rows frames and <= max_items motions
-        motions = [(i, j) for i, nb in enumerate(Bs) for j in range(nb)]
-        groups, cur, rows = [], [], 0
-        for (i, j) in motions:
-            if cur and (rows + Ts[i] > max_rows or len(cur) >= max_items):
-                groups.append(cur)
-                cur, rows = [], 0
-            cur.append((i, j))
-            rows += Ts[i]
-        if cur:
-            groups.append(cur)
-        gmax_items = max(len(g) for g in groups)
-        gmax_rows = max(sum(Ts[i] for i, _ in g) for g in groups)
+        groups = pack_groups(Bs, Ts, max_rows, max_items)
         Tm = max(max(Ts), self.num_frames)
-        smp = self._sampler_for(max(gmax_items, -(-gmax_rows // Tm)), Tm)
-        self._set_schedule_on(smp, sch)
-        wi = 262 if m.mixing_mode >= 3 else 1
-        outs = [[None] * nb for nb in Bs]
-        hists = [[None] * nb for nb in Bs]
-        pend = []
+        smp = self._sampler_for(_handle_batch(groups, Ts, Tm), Tm)
+        smp.use_schedule(sch)
         steps = sch.num_timesteps - skip
-        if form == "noise":
-            for i, b in enumerate(batches):
-                sn = b["step_noise"]
-                if sn.dim() != 4 or sn.shape[0] < steps or tuple(sn.shape[1:]) != (Bs[i], Ts[i], 524):
-                    raise ValueError(f"sample_many: batch {i}: step_noise [>= {steps}, {Bs[i]}, {Ts[i]}, 524] expected, got {tuple(sn.shape)}")
-        for k in ("x_start", "init_image"):
-            for i, b in enumerate(batches):
-                if b.get(k) is not None and (b[k].dim() != 3 or b[k].shape[0] != Bs[i]):
-                    raise ValueError(f"sample_many: batch {i}: {k} [{Bs[i]}, T, 524] expected, got {tuple(b[k].shape)}")
-        if eta:
-            smp.set_eta(eta)
-        try:
-            for g in groups:
-                lens = [Ts[i] for i, _ in g]
-                need = slots * 2 * (sum(lens) + 128) * 4 * sum(wi if n.startswith("influence") else 524 for n in names)
-                if need > HISTORY_BUDGET_BYTES:
-                    raise MemoryError(f"history side outputs of a ragged batch of {sum(lens)} frames need {need / 2**30:.1f} GiB; lower max_rows, set "
-                                      "model.history_every, or pass keep_history=False")
-                cond_g = torch.cat([conds[i][j:j + 1] for i, j in g], 0)
-                x_g = [xs[i][j] for i, j in g]
-                kw = {}
-                if use_opts:                              # motion j of batch i: (seed_i, noise row j), or its slice of the batch's buffers
-                    kw["skip_timesteps"] = skip
-                    if form == "seed":
-                        kw["seeds"], kw["noise_rows"] = [seeds[i] for i, _ in g], [j for _, j in g]
-                    elif form == "noise":
-                        kw["noise"] = [batches[i]["step_noise"][:steps, j] for i, j in g]
-                    for k in ("x_start", "init_image"):
-                        if batches[g[0][0]].get(k) is not None:
-                            kw[k] = [batches[i][k][j] for i, j in g]
-                items, hist, ev = smp.sample_ragged_async(cond_g, x_g, lens, history=names or None, history_every=self.history_every, **kw)
-                pend.append((g, items, hist, ev, smp.item_slices(), smp.rows))
-        finally:
-            if eta:                                       # eta belongs to this call: the handle is left at eta = 0, as _run_loop_on leaves it
-                smp.set_eta(0.0)
-        for g, items, hist, ev, slices, rows in pend:
-            ev.synchronize()
-            for (i, j), it, (o, t) in zip(g, items, slices):
-                outs[i][j] = it
-                if hist:
-                    # the reference's [2B, T, C] history rows of this motion: its cond row and its uncond row
-                    hists[i][j] = {k: (v[:, 0, o:o + t], v[:, 1, o:o + t]) for k, v in hist.items()}
-        torch.cuda.current_stream(dev).wait_stream(smp.stream)
+        _check_loop_shapes(batches, form, Bs, Ts, steps, "sample_many", 524)
+
+        def budget(frames):
+            need = per_row * (frames + 128)
+            if need > HISTORY_BUDGET_BYTES:
+                raise MemoryError(f"history side outputs of a ragged batch of {frames} frames need {need / 2**30:.1f} GiB; lower max_rows, set "
+                                  "model.history_every, or pass keep_history=False")
+
+        options = [_group_options(g, form, seeds, batches, steps, skip) if use_opts else {} for g in groups]
+        outs, hists = _run_groups(smp, groups, conds, xs, Ts, options, eta, history=names, history_every=self.history_every, budget=budget)
         for i, nb in enumerate(Bs):
             results[i]["output"] = torch.stack(outs[i], 0)
             if names:
@@ -687,7 +605,346 @@ class MixerMDM(nn.Module):
         return {"output": output, "influence_i1": m.history_influence_i1, "influence_i2": m.history_influence_i2}
 
 
-class in2INDiffusion(nn.Module):
+# ---- stand-alone in2IN, InterGen and MDM samplers; what the many-call drivers share ----------------------------------------------------
+def _unwrap_checkpoint(state_dict):
+    """A raw state dict, or a Lightning checkpoint {"state_dict": {"model.<key>": ...}} (mixermdm.py:43-59): the ``model.`` prefix is dropped."""
+    sd = state_dict["state_dict"] if "state_dict" in state_dict and isinstance(state_dict["state_dict"], dict) else state_dict
+    if sd and all(k.startswith("model.") for k in sd):
+        sd = {k[len("model."):]: v for k, v in sd.items()}
+    return dict(sd)
+
+
+def _unsupported(fn, *a, **k):
+    """Runs a sampler call; a refusal of the library (MMDM_ERR_UNSUPPORTED) becomes NotImplementedError with the library's message."""
+    from ._lib import MMDMError
+    try:
+        return fn(*a, **k)
+    except MMDMError as e:
+        if e.status == _KeyMask.UNSUPPORTED:
+            raise NotImplementedError(str(e)) from None
+        raise
+
+
+def _draw_seed():
+    """An un-named seed comes from torch's default generator: torch.manual_seed reproduces a run."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+def _loop_forms(batches, eta, skip, who, no_opts=None):
+    """The rules of a many-call for the loop arguments a batch dict may carry: 'x_start' / 'init_image' for every batch or for none; at eta > 0
+    ONE noise form per call -- 'seed' (an un-named one is drawn, in batch order) or 'step_noise'.  no_opts: the refusal of a caller that takes none
+    of the options.  -> (any option in use, form "seed" | "noise" | None, seeds per batch)."""
+    has = lambda k: [b.get(k) is not None for b in batches]
+    for k in ("x_start", "init_image"):
+        if any(has(k)) and not all(has(k)):
+            raise ValueError(f"{who}: batch {has(k).index(not has(k)[0])} differs from batch 0 in whether it gives {k!r}: give it for every batch or for none")
+    use_opts = bool(eta or skip or any(has("x_start")) or any(has("init_image")))
+    if use_opts and no_opts:
+        raise ValueError(f"{who}: {no_opts}")
+    form, seeds = None, [None] * len(batches)
+    if eta:
+        for i, b in enumerate(batches):
+            sd, sn = b.get("seed"), b.get("step_noise")
+            if sd is not None and sn is not None:
+                raise ValueError(f"{who}: batch {i} gives both 'seed' and 'step_noise'")
+            f = "noise" if sn is not None else "seed"
+            if form is not None and f != form:
+                raise ValueError(f"{who}: batch {i} names its step noise as a {f!r}, batch 0 as a {form!r}: one noise form per call")
+            form = f
+            if f == "seed":
+                seeds[i] = int(sd) if sd is not None else _draw_seed()
+    return use_opts, form, seeds
+
+
+def _check_loop_shapes(batches, form, Bs, Ts, steps, who, width):
+    """The shapes of a many-call's 'step_noise' (form "noise"), 'x_start' and 'init_image' entries against their batch's (b, T)."""
+    if form == "noise":
+        for i, b in enumerate(batches):
+            sn = b["step_noise"]
+            if sn.dim() != 4 or sn.shape[0] < steps or tuple(sn.shape[1:]) != (Bs[i], Ts[i], width):
+                raise ValueError(f"{who}: batch {i}: step_noise [>= {steps}, {Bs[i]}, {Ts[i]}, {width}] expected, got {tuple(sn.shape)}")
+    for k in ("x_start", "init_image"):
+        for i, b in enumerate(batches):
+            if b.get(k) is not None and (b[k].dim() != 3 or b[k].shape[0] != Bs[i]):
+                raise ValueError(f"{who}: batch {i}: {k} [{Bs[i]}, T, {width}] expected, got {tuple(b[k].shape)}")
+
+
+def _group_options(g, form, seeds, batches, steps, skip):
+    """sample_ragged_async's keywords for the group g of a many-call with options: motion j of batch i draws (seed_i, noise row j), or takes its slice
+    of the batch's buffers."""
+    kw = {"skip_timesteps": skip}
+    if form == "seed":
+        kw["seeds"], kw["noise_rows"] = [seeds[i] for i, _ in g], [j for _, j in g]
+    elif form == "noise":
+        kw["noise"] = [batches[i]["step_noise"][:steps, j] for i, j in g]
+    for k in ("x_start", "init_image"):
+        if batches[g[0][0]].get(k) is not None:
+            kw[k] = [batches[i][k][j] for i, j in g]
+    return kw
+
+
+def _loop_call(s, cond, x_T, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0, start_step=None):
+    """One sampling call with the loop's other arguments on a sampler that takes them (single_only 0 / 4).  eta > 0 needs its step noise: step_noise
+    [>= S - skip, B, T, 524] or seed (the device generator; with neither, a seed is drawn from torch's default generator).  eta belongs to the call."""
+    eta = float(eta)
+    if eta < 0:
+        raise ValueError(f"eta={eta} must be >= 0")
+    if step_noise is not None and seed is not None:
+        raise ValueError("give the step noise as a buffer (step_noise=) or as a seed (seed=), not both")
+    if eta == 0.0:
+        step_noise = seed = None
+    elif step_noise is None and seed is None:
+        seed = _draw_seed()
+    S, skip = s.schedule.num_timesteps, int(skip_timesteps)
+    if not 0 <= skip < S:
+        raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
+    try:
+        kw = dict(eta=eta, noise=step_noise[:S - skip] if step_noise is not None else None, seed=seed, x_start=x_start, init_image=init_image, skip_timesteps=skip)
+        if start_step is not None:
+            return s.sample_from(cond, x_T, start_step, **kw)
+        return s.sample(cond, x_T, **kw)
+    finally:
+        if eta:
+            s.set_eta(0.0)
+
+
+def _refusable_loop_call(s, cond, x_T, loop_kw):
+    """The same call on a sampler that refuses the loop's arguments (single_only 1 / 2 / 3): whatever is given is handed to the library, whose refusal
+    comes back as NotImplementedError with its message."""
+    kw = {k: v for k, v in loop_kw.items() if v is not None and not (k in ("eta", "skip_timesteps") and not v)}
+    if "step_noise" in kw:
+        kw["noise"] = kw.pop("step_noise")
+    if kw.get("eta") and "noise" not in kw and "seed" not in kw:
+        kw["seed"] = 0
+    if "start_step" in kw:
+        return _unsupported(s.sample_from, cond, x_T, kw.pop("start_step"), **kw)
+    return _unsupported(s.sample, cond, x_T, **kw)
+
+
+def pack_groups(Bs, Ts, max_rows=4800, max_items=64):
+    """The packing rule of sample_many / invert_many: the motions (batch i, row j) in batch order, cut into ragged groups of <= max_rows frames and
+    <= max_items motions (a motion longer than max_rows is a group of its own).  -> list of groups, each a list of (i, j)."""
+    groups, cur, rows = [], [], 0
+    for i, nb in enumerate(Bs):
+        for j in range(nb):
+            if cur and (rows + Ts[i] > max_rows or len(cur) >= max_items):
+                groups.append(cur)
+                cur, rows = [], 0
+            cur.append((i, j))
+            rows += Ts[i]
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def _handle_batch(groups, Ts, Tm):
+    """max_batch of the handle of max_frames = Tm that takes every group: its motions, and its frames as rows of the workspace."""
+    return max(max(len(g) for g in groups), -(-max(sum(Ts[i] for i, _ in g) for g in groups) // Tm))
+
+
+def _run_groups(smp, groups, conds, xs, Ts, options, eta=0.0, history=None, history_every=1, budget=None):
+    """The ragged launch loop of a many-call: every group queued on the sampler's stream with its keywords (options[k]), eta the call's (the handle is left
+    at eta = 0, as a single call leaves it), then the items handed back to their (batch, row).  conds / xs: per batch [b, .] and [b, T, C].  history: the
+    names to keep (a list, possibly empty: the two-chain sampler) or None (the one-chain samplers keep none); budget(frames) may refuse a group.
+    -> (outs[i][j] = [T_i, C], hists[i][j] = {name: (cond rows, uncond rows), each [slots, T_i, C]} or None): the caller's stream is behind the sampler's."""
+    outs = [[None] * len(x) for x in xs]
+    hists = [[None] * len(x) for x in xs]
+    hkw = {} if history is None else dict(history=history or None, history_every=history_every)
+    pend = []
+    if eta:
+        smp.set_eta(eta)
+    try:
+        for g, kw in zip(groups, options):
+            lens = [Ts[i] for i, _ in g]
+            if budget is not None:
+                budget(sum(lens))
+            items, hist, ev = smp.sample_ragged_async(torch.cat([conds[i][j:j + 1] for i, j in g], 0), [xs[i][j] for i, j in g], lens, **hkw, **kw)
+            pend.append((g, items, hist, ev, smp.item_slices() if hist else None))
+    finally:
+        if eta:
+            smp.set_eta(0.0)
+    for g, items, hist, ev, slices in pend:
+        ev.synchronize()
+        for k, (i, j) in enumerate(g):
+            outs[i][j] = items[k]
+            if hist:                                      # the reference's [2B, T, C] history rows of this motion: its cond row and its uncond row
+                o, t = slices[k]
+                hists[i][j] = {n: (v[:, 0, o:o + t], v[:, 1, o:o + t]) for n, v in hist.items()}
+    torch.cuda.current_stream(smp.device).wait_stream(smp.stream)
+    return outs, hists
+
+
+def _invert_inputs(model, batch):
+    """(cond, x_0, B, T) of an inversion call: the model's cond entries and batch["motions"] [B, T, WIDTH]."""
+    if batch.get("motions") is None:
+        raise ValueError(f"{type(model).__name__}.invert: the batch gives no 'motions' [B, T, {model.WIDTH}]")
+    m = batch["motions"]
+    if m.dim() != 3:
+        raise ValueError(f"{type(model).__name__}.invert: motions [B, T, {model.WIDTH}] expected, got {tuple(m.shape)}")
+    return model._inputs(dict(batch, x_T=m, motion_lens=[m.shape[1]]))
+
+
+def _invert(model, batch, steps):
+    from .sampler import invert_steps
+    cond, x_0, B, T = _invert_inputs(model, batch)
+    s = model._get_sampler(B, T)
+    k = invert_steps(steps, s.schedule.num_timesteps)
+    return {"latent": _unsupported(s.invert, cond, x_0, k), "steps": k}
+
+
+def _invert_many(model, batches, batching, steps, max_rows, max_items):
+    from .sampler import invert_steps
+    who = f"{type(model).__name__}.invert_many"
+    if batching not in ("sequential", "ragged"):
+        raise ValueError(f'{who}: batching {batching!r} not recognized ("ragged" or "sequential")')
+    if batching == "sequential":
+        return [_invert(model, b, steps) for b in batches]
+    ins = [_invert_inputs(model, b) for b in batches]
+    Bs, Ts = [v[2] for v in ins], [v[3] for v in ins]
+    groups = pack_groups(Bs, Ts, max_rows, max_items)
+    Tm = max(max(Ts), model.num_frames)
+    smp = model._get_sampler(_handle_batch(groups, Ts, Tm), Tm)
+    k = invert_steps(steps, smp.schedule.num_timesteps)
+    outs = [[None] * nb for nb in Bs]
+    for g in groups:
+        items = _unsupported(smp.invert_ragged, torch.cat([ins[i][0][j:j + 1] for i, j in g], 0), [ins[i][1][j] for i, j in g], [Ts[i] for i, _ in g], k)
+        for (i, j), it in zip(g, items):
+            outs[i][j] = it
+    return [{"latent": torch.stack(o, 0), "steps": k} for o in outs]
+
+
+class _StandaloneDiffusion(nn.Module):
+    """What in2INDiffusion, InterDiffusion and MDM share: parameters under the reference's names, one Sampler handle, the schedule, ragged batching of many calls."""
+    WIDTH = 524
+    _who = None               # the model's name in the "MI355X only" refusal, when it is not the class name
+    _loop_options = True      # False: the handle refuses the loop's options (eta, skip_timesteps, x_start, init_image) by name
+
+    def _apply(self, fn, recurse=True):
+        self._dirty = True
+        return super()._apply(fn, recurse)
+
+    @property
+    def device(self):
+        return next(self.parameters()).device
+
+    def load_state_dict(self, state_dict, strict=True):
+        sd = {k: v for k, v in state_dict.items() if not k.endswith("sequence_pos_encoder.pe")}
+        self._dirty = True
+        return super().load_state_dict(sd, strict=strict)
+
+    def _handle_kind(self, legacy):
+        """The Sampler keywords that tell the model's handle variants apart (none by default)."""
+        return {}
+
+    def _on_schedule(self, s):
+        """Runs after the handle took a new schedule."""
+
+    def _get_sampler(self, B, T, legacy=False):
+        """The one handle of the model, loaded and on the model's schedule.  A handle is re-built when the variant (_handle_kind(legacy), precision) or the
+        device changes or it is too small; growth keeps the previous max_batch of the same variant."""
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"{self._who or type(self).__name__} runs on an MI355X only: call .to('cuda:N') first (no CPU path)")
+        kind = (self._handle_kind(legacy), self.precision)
+        s = self._sampler
+        same = s is not None and s._kind == kind
+        if not same or B > s.cfg.max_batch or T > s.cfg.max_frames or s.device != dev:
+            grow = s.cfg.max_batch if same else 1
+            if s is not None:
+                s.close()
+            s = self._make_sampler(max(B, grow), max(T, self.num_frames), dev, **kind[0])
+            s._kind = kind
+            self._sampler, self._dirty = s, True
+        if self._dirty:
+            s.load_state_dict(self._sampler_state())
+            s.prepare()
+            s._strategy = None
+            self._dirty = False
+        if s._strategy != self.sampling_strategy:
+            s.set_schedule(self.sampling_strategy, self.beta_scheduler, self.diffusion_steps)
+            self._on_schedule(s)
+            s._strategy = self.sampling_strategy
+        return s
+
+    def _inputs(self, batch):
+        cond = batch["cond"]
+        B, T = cond.shape[0], int(batch["motion_lens"][0])
+        x_T = batch["x_T"] if batch.get("x_T") is not None else torch.randn(B, T, self.WIDTH, device=self.device)
+        if tuple(x_T.shape) != (B, T, self.WIDTH):
+            raise ValueError(f"{type(self).__name__}: x_T [{B}, {T}, {self.WIDTH}] expected, got {tuple(x_T.shape)}")
+        return cond, x_T, B, T
+
+    def _sample_many(self, batches, batching, max_rows, max_items, eta=0.0, skip_timesteps=0):
+        who = f"{type(self).__name__}.sample_many"
+        if batching not in ("sequential", "ragged"):
+            raise ValueError(f'{who}: batching {batching!r} not recognized ("ragged" or "sequential")')
+        eta, skip = float(eta), int(skip_timesteps)
+        if eta < 0:
+            raise ValueError(f"eta={eta} must be >= 0")
+        use_opts, form, seeds = _loop_forms(batches, eta, skip, who)
+        if use_opts and not self._loop_options:
+            # the library decides: its refusal (mode 1 keeps the option refusals) comes back as NotImplementedError with its message
+            cond, x_T, B, T = self._inputs(batches[0])
+            _unsupported(self._get_sampler(B, T).sample, cond, x_T, eta=eta, skip_timesteps=skip, seed=seeds[0], x_start=batches[0].get("x_start"),
+                         init_image=batches[0].get("init_image"))
+            raise NotImplementedError(f"{who}: the loop options are not covered by this sampler")
+        if batching == "sequential":
+            out = []
+            for i, b in enumerate(batches):
+                kw = dict(eta=eta, skip_timesteps=skip, seed=seeds[i], step_noise=b.get("step_noise") if form == "noise" else None,
+                          x_start=b.get("x_start"), init_image=b.get("init_image")) if use_opts else {}
+                out.append({"output": self.forward(b, **kw)["output"]})
+            return out
+        ins = [self._inputs(b) for b in batches]
+        Bs, Ts = [v[2] for v in ins], [v[3] for v in ins]
+        groups = pack_groups(Bs, Ts, max_rows, max_items)
+        Tm = max(max(Ts), self.num_frames)
+        smp = self._get_sampler(_handle_batch(groups, Ts, Tm), Tm)
+        S = smp.schedule.num_timesteps
+        if not 0 <= skip < S:
+            raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
+        _check_loop_shapes(batches, form, Bs, Ts, S - skip, who, self.WIDTH)
+        options = [_group_options(g, form, seeds, batches, S - skip, skip) if use_opts else {} for g in groups]
+        outs, _ = _run_groups(smp, groups, [v[0] for v in ins], [v[1] for v in ins], Ts, options, eta)
+        return [{"output": torch.stack(o, 0)} for o in outs]
+
+    def invert(self, batch, steps=None):
+        """DDIM inversion of batch["motions"] [B, T, WIDTH] (normalised space) under batch["cond"] -> {"latent": [B, T, WIDTH], "steps": k}: the chain at
+        respaced step k (None = all S steps: the x_T of a plain forward).  For k < S, forward(dict(batch, x_T=latent), start_step=k) walks the same levels
+        down again."""
+        return _invert(self, batch, steps)
+
+    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
+        """invert for many batches with sample_many's packing: every latent bit-identical to that batch's own invert call."""
+        return _invert_many(self, batches, batching, steps, max_rows, max_items)
+
+
+class _TextStage:
+    """sample_many / invert / invert_many of the text facades (in2IN, InterGen, MDM): the stand-alone sampler's (``_sampler_model``: the facade's
+    ``decoder``; MDM is its own) after the text stage.  The one hook: ``_with_cond(batch)`` fills the sampler's cond entries into the batch (a copy; called
+    under no_grad).  A class that names an existing method as the hook (``_with_cond = text_process``) binds it as the class is created: a subclass that
+    overrides that method names it again."""
+    _sampler_model = property(lambda self: self.decoder)
+
+    def _conds(self, batches):
+        with torch.no_grad():
+            return [self._with_cond(dict(b)) for b in batches]
+
+    def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
+        """The sampler's sample_many (InterDiffusion.sample_many) after the text stage -> one {"output"} per batch, every motion bit-identical to the
+        sequential calls.  mode / inflight / keep_history are accepted for generate_for_evaluation's call and unused (one chain, no history side outputs)."""
+        return self._sampler_model._sample_many(self._conds(batches), batching, max_rows, max_items, eta, skip_timesteps)
+
+    def invert(self, batch, steps=None):
+        """The sampler's invert after the text stage: batch["motions"] [B, T, WIDTH] under the batch's text / cond entries -> {"latent", "steps"}."""
+        return _invert(self._sampler_model, self._conds([batch])[0], steps)
+
+    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
+        """The sampler's invert_many after the text stage: every latent bit-identical to that batch's own invert call."""
+        return _invert_many(self._sampler_model, self._conds(batches), batching, steps, max_rows, max_items)
+
+
+class in2INDiffusion(_StandaloneDiffusion):
     """Stand-alone sub-model sampler: in2INDiffusion.forward (src/models/in2in.py:285-356), modes "individual"
     (ClassifierFreeSampleModel, [B,T,262]), "interaction" (ClassifierFreeSampleModelMultiple, [B,T,524]) and "dual"
     (ClassifierFreeSampleDualMDM over net_individual + net_interaction, [B,T,524]); output stays in the model's normalised
@@ -696,6 +953,8 @@ class in2INDiffusion(nn.Module):
     the loop's other arguments (GaussianDiffusion.ddim_sample_loop, gaussian_diffusion.py:946-1069) and ragged batches -- except a call with an explicit
     ``mask``, which builds the single_only 2 / 3 handle and gets its refusal by name; "individual" stays on single_only=1, whose refusal of the loop's
     arguments comes back as NotImplementedError.  ``.precision`` picks the handle's mode."""
+
+    _who = "in2IN"
 
     def __init__(self, cfg, mode, sampling_strategy="ddim50"):
         super().__init__()
@@ -725,51 +984,28 @@ class in2INDiffusion(nn.Module):
                 _holder_tree(self, k, torch.zeros(shp))
         self._sampler, self._dirty = None, True
 
-    def _apply(self, fn, recurse=True):
-        self._dirty = True
-        return super()._apply(fn, recurse)
-
-    def load_state_dict(self, state_dict, strict=True):
-        sd = {k: v for k, v in state_dict.items() if not k.endswith("sequence_pos_encoder.pe")}
-        self._dirty = True
-        return super().load_state_dict(sd, strict=strict)
+    def _handle_kind(self, legacy):
+        """legacy: the single_only 2 / 3 handle of "interaction" / "dual" (a call with a mask)."""
+        return {"individual": dict(single_only=1), "interaction": dict(single_only=2) if legacy else dict(single_only=4, cfg_form=1),
+                "dual": dict(single_only=3) if legacy else dict(single_only=4, cfg_form=2)}[self.mode]
 
     @property
-    def device(self):
-        return next(self.parameters()).device
+    def _loop_options(self):
+        return self.mode != "individual"
 
-    def _get_sampler(self, B, T, legacy=False):
-        """The handle of the mode, loaded and on the model's schedule.  legacy: the single_only 2 / 3 handle of "interaction" / "dual" (a call with a mask)."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("in2IN runs on an MI355X only: call .to('cuda:N') first (no CPU path)")
-        kind = {"individual": dict(single_only=1), "interaction": dict(single_only=2) if legacy else dict(single_only=4, cfg_form=1),
-                "dual": dict(single_only=3) if legacy else dict(single_only=4, cfg_form=2)}[self.mode]
-        s = self._sampler
-        same = s is not None and s._kind == (kind, self.precision)
-        if not same or B > s.cfg.max_batch or T > s.cfg.max_frames or s.device != dev:
-            grow = s.cfg.max_batch if same else 1
-            if s is not None:
-                s.close()
-            s = Sampler(d_heads=self.num_heads, cfg_scale=self.cfg_weight, cfg_scale_interaction=self.cfg_weight_interaction,
-                        cfg_scale_individual=self.cfg_weight_individual, max_batch=max(B, grow), max_frames=max(T, self.num_frames), device=dev,
-                        precision=self.precision, **kind, **self.dims)
-            s._kind = (kind, self.precision)
-            self._sampler, self._dirty = s, True
-        if self._dirty:
-            sd = {}
-            for net, pfx in self._nets:
-                sd.update({pfx + k[len(net) + 1:]: p.data for k, p in self.named_parameters() if k.startswith(net + ".")})
-            s.load_state_dict(sd)
-            s.prepare()
-            s._strategy = None
-            self._dirty = False
-        if s._strategy != self.sampling_strategy:
-            s.set_schedule(self.sampling_strategy, self.beta_scheduler, self.diffusion_steps)
-            if self.mode == "dual":
-                s.set_dual_weights(self.cfg_composition_weight_func, self.cfg_composition_weight_value)
-            s._strategy = self.sampling_strategy
-        return s
+    def _make_sampler(self, B, T, dev, **kind):
+        return Sampler(d_heads=self.num_heads, cfg_scale=self.cfg_weight, cfg_scale_interaction=self.cfg_weight_interaction,
+                       cfg_scale_individual=self.cfg_weight_individual, max_batch=B, max_frames=T, device=dev, precision=self.precision, **kind, **self.dims)
+
+    def _sampler_state(self):
+        sd = {}
+        for net, pfx in self._nets:
+            sd.update({pfx + k[len(net) + 1:]: p.data for k, p in self.named_parameters() if k.startswith(net + ".")})
+        return sd
+
+    def _on_schedule(self, s):
+        if self.mode == "dual":
+            s.set_dual_weights(self.cfg_composition_weight_func, self.cfg_composition_weight_value)
 
     def _inputs(self, batch):
         if self.mode == "dual":                      # in2in.py:299-305
@@ -801,20 +1037,10 @@ class in2INDiffusion(nn.Module):
     def sample_many(self, batches, batching="ragged", max_rows=4800, max_items=64, *, eta=0.0, skip_timesteps=0):
         """InterDiffusion.sample_many for this model: batch dicts as forward takes them, every motion bit-identical to that batch's own forward call.
         Mode "individual" runs ragged without the loop's options (NotImplementedError with the library's message otherwise)."""
-        return _StandaloneDiffusion._sample_many(self, batches, batching, max_rows, max_items, eta, skip_timesteps, options=self.mode != "individual")
-
-    def invert(self, batch, steps=None):
-        """DDIM inversion of batch["motions"] [B, T, WIDTH] (normalised space) under the batch's cond_* entries -> {"latent": [B, T, WIDTH], "steps": k}: the
-        chain at respaced step k (None = all S steps: the x_T of a plain forward).  For k < S, forward(dict(batch, x_T=latent), start_step=k) walks the
-        same levels down again."""
-        return _invert(self, batch, steps)
-
-    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
-        """invert for many batches with sample_many's packing: every latent bit-identical to that batch's own invert call."""
-        return _invert_many(self, batches, batching, steps, max_rows, max_items)
+        return self._sample_many(batches, batching, max_rows, max_items, eta, skip_timesteps)
 
 
-class in2IN(nn.Module):
+class in2IN(_TextStage, nn.Module):
     """in2IN(cfg, mode) facade (src/models/in2in.py:14-135) around the stand-alone sampler.  Text conditioning: when the loaded checkpoint
     carries the CLIP tower and the clipTransEncoder_{individual,interaction} heads (in2in.py:24-69), ``text_process`` runs them on the GPU
     (mixermdm_amd.text); otherwise pass the encoded ``cond_*`` entries in the batch or register ``text_encoder(batch, mode, text_name, out_name)``."""
@@ -887,296 +1113,7 @@ class in2IN(nn.Module):
             batch = self.text_process(batch, "individual", out_name="cond_individual_individual1")
         return batch
 
-    def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
-        """in2INDiffusion.sample_many after forward_test's text stage; mode / inflight / keep_history are accepted for generate_for_evaluation's call and
-        unused (one chain, no history side outputs)."""
-        with torch.no_grad():
-            batches = [self._text_all(dict(b)) for b in batches]
-        return self.decoder.sample_many(batches, batching=batching, max_rows=max_rows, max_items=max_items, eta=eta, skip_timesteps=skip_timesteps)
-
-    def invert(self, batch, steps=None):
-        """in2INDiffusion.invert after forward_test's text stage."""
-        with torch.no_grad():
-            batch = self._text_all(dict(batch))
-        return self.decoder.invert(batch, steps)
-
-    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
-        """in2INDiffusion.invert_many after forward_test's text stage."""
-        with torch.no_grad():
-            batches = [self._text_all(dict(b)) for b in batches]
-        return self.decoder.invert_many(batches, batching=batching, steps=steps, max_rows=max_rows, max_items=max_items)
-
-
-# ---- stand-alone InterGen and MDM samplers ---------------------------------------------------------------------------------------
-def _unwrap_checkpoint(state_dict):
-    """A raw state dict, or a Lightning checkpoint {"state_dict": {"model.<key>": ...}} (mixermdm.py:43-59): the ``model.`` prefix is dropped."""
-    sd = state_dict["state_dict"] if "state_dict" in state_dict and isinstance(state_dict["state_dict"], dict) else state_dict
-    if sd and all(k.startswith("model.") for k in sd):
-        sd = {k[len("model."):]: v for k, v in sd.items()}
-    return dict(sd)
-
-
-def _unsupported(fn, *a, **k):
-    """Runs a sampler call; a refusal of the library (MMDM_ERR_UNSUPPORTED) becomes NotImplementedError with the library's message."""
-    from ._lib import MMDMError
-    try:
-        return fn(*a, **k)
-    except MMDMError as e:
-        if e.status == _KeyMask.UNSUPPORTED:
-            raise NotImplementedError(str(e)) from None
-        raise
-
-
-def _loop_forms(batches, eta, who):
-    """MixerMDM.sample_many's rules for the loop arguments a batch dict may carry: 'x_start' / 'init_image' for every batch or for none; at eta > 0
-    ONE noise form per call -- 'seed' (an un-named one is drawn from torch's default generator, in batch order) or 'step_noise'.
-    -> (form "seed" | "noise" | None, seeds per batch)."""
-    has = lambda k: [b.get(k) is not None for b in batches]
-    for k in ("x_start", "init_image"):
-        if any(has(k)) and not all(has(k)):
-            raise ValueError(f"{who}: batch {has(k).index(not has(k)[0])} differs from batch 0 in whether it gives {k!r}: give it for every batch or for none")
-    form, seeds = None, [None] * len(batches)
-    if eta:
-        for i, b in enumerate(batches):
-            sd, sn = b.get("seed"), b.get("step_noise")
-            if sd is not None and sn is not None:
-                raise ValueError(f"{who}: batch {i} gives both 'seed' and 'step_noise'")
-            f = "noise" if sn is not None else "seed"
-            if form is not None and f != form:
-                raise ValueError(f"{who}: batch {i} names its step noise as a {f!r}, batch 0 as a {form!r}: one noise form per call")
-            form = f
-            if f == "seed":
-                seeds[i] = int(sd) if sd is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-    return form, seeds
-
-
-def _loop_call(s, cond, x_T, eta=0.0, seed=None, step_noise=None, x_start=None, init_image=None, skip_timesteps=0, start_step=None):
-    """One sampling call with the loop's other arguments on a sampler that takes them (single_only 0 / 4).  eta > 0 needs its step noise: step_noise
-    [>= S - skip, B, T, 524] or seed (the device generator; with neither, a seed is drawn from torch's default generator).  eta belongs to the call."""
-    eta = float(eta)
-    if eta < 0:
-        raise ValueError(f"eta={eta} must be >= 0")
-    if step_noise is not None and seed is not None:
-        raise ValueError("give the step noise as a buffer (step_noise=) or as a seed (seed=), not both")
-    if eta == 0.0:
-        step_noise = seed = None
-    elif step_noise is None and seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    S, skip = s.schedule.num_timesteps, int(skip_timesteps)
-    if not 0 <= skip < S:
-        raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
-    try:
-        kw = dict(eta=eta, noise=step_noise[:S - skip] if step_noise is not None else None, seed=seed, x_start=x_start, init_image=init_image, skip_timesteps=skip)
-        if start_step is not None:
-            return s.sample_from(cond, x_T, start_step, **kw)
-        return s.sample(cond, x_T, **kw)
-    finally:
-        if eta:
-            s.set_eta(0.0)
-
-
-def _refusable_loop_call(s, cond, x_T, loop_kw):
-    """The same call on a sampler that refuses the loop's arguments (single_only 1 / 2 / 3): whatever is given is handed to the library, whose refusal
-    comes back as NotImplementedError with its message."""
-    kw = {k: v for k, v in loop_kw.items() if v is not None and not (k in ("eta", "skip_timesteps") and not v)}
-    if "step_noise" in kw:
-        kw["noise"] = kw.pop("step_noise")
-    if kw.get("eta") and "noise" not in kw and "seed" not in kw:
-        kw["seed"] = 0
-    if "start_step" in kw:
-        return _unsupported(s.sample_from, cond, x_T, kw.pop("start_step"), **kw)
-    return _unsupported(s.sample, cond, x_T, **kw)
-
-
-def pack_groups(Bs, Ts, max_rows=4800, max_items=64):
-    """The packing rule of sample_many / invert_many: the motions (batch i, row j) in batch order, cut into ragged groups of <= max_rows frames and
-    <= max_items motions (a motion longer than max_rows is a group of its own).  -> list of groups, each a list of (i, j)."""
-    groups, cur, rows = [], [], 0
-    for i, nb in enumerate(Bs):
-        for j in range(nb):
-            if cur and (rows + Ts[i] > max_rows or len(cur) >= max_items):
-                groups.append(cur)
-                cur, rows = [], 0
-            cur.append((i, j))
-            rows += Ts[i]
-    if cur:
-        groups.append(cur)
-    return groups
-
-
-def _invert_inputs(model, batch):
-    """(cond, x_0, B, T) of an inversion call: the model's cond entries and batch["motions"] [B, T, WIDTH]."""
-    if batch.get("motions") is None:
-        raise ValueError(f"{type(model).__name__}.invert: the batch gives no 'motions' [B, T, {model.WIDTH}]")
-    m = batch["motions"]
-    if m.dim() != 3:
-        raise ValueError(f"{type(model).__name__}.invert: motions [B, T, {model.WIDTH}] expected, got {tuple(m.shape)}")
-    return model._inputs(dict(batch, x_T=m, motion_lens=[m.shape[1]]))
-
-
-def _invert(model, batch, steps):
-    from .sampler import invert_steps
-    cond, x_0, B, T = _invert_inputs(model, batch)
-    s = model._get_sampler(B, T)
-    k = invert_steps(steps, s.schedule.num_timesteps)
-    return {"latent": _unsupported(s.invert, cond, x_0, k), "steps": k}
-
-
-def _invert_many(model, batches, batching, steps, max_rows, max_items):
-    from .sampler import invert_steps
-    who = f"{type(model).__name__}.invert_many"
-    if batching not in ("sequential", "ragged"):
-        raise ValueError(f'{who}: batching {batching!r} not recognized ("ragged" or "sequential")')
-    if batching == "sequential":
-        return [_invert(model, b, steps) for b in batches]
-    ins = [_invert_inputs(model, b) for b in batches]
-    Bs, Ts = [v[2] for v in ins], [v[3] for v in ins]
-    groups = pack_groups(Bs, Ts, max_rows, max_items)
-    Tm = max(max(Ts), model.num_frames)
-    smp = model._get_sampler(max(max(len(g) for g in groups), -(-max(sum(Ts[i] for i, _ in g) for g in groups) // Tm)), Tm)
-    k = invert_steps(steps, smp.schedule.num_timesteps)
-    outs = [[None] * nb for nb in Bs]
-    for g in groups:
-        items = _unsupported(smp.invert_ragged, torch.cat([ins[i][0][j:j + 1] for i, j in g], 0), [ins[i][1][j] for i, j in g], [Ts[i] for i, _ in g], k)
-        for (i, j), it in zip(g, items):
-            outs[i][j] = it
-    return [{"latent": torch.stack(o, 0), "steps": k} for o in outs]
-
-
-class _StandaloneDiffusion(nn.Module):
-    """What InterDiffusion and MDM share: parameters under the reference's names, one Sampler handle, the schedule, ragged batching of many calls."""
-    WIDTH = 524
-
-    def _apply(self, fn, recurse=True):
-        self._dirty = True
-        return super()._apply(fn, recurse)
-
-    @property
-    def device(self):
-        return next(self.parameters()).device
-
-    def load_state_dict(self, state_dict, strict=True):
-        sd = {k: v for k, v in state_dict.items() if not k.endswith("sequence_pos_encoder.pe")}
-        self._dirty = True
-        return super().load_state_dict(sd, strict=strict)
-
-    def _get_sampler(self, B, T):
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} runs on an MI355X only: call .to('cuda:N') first (no CPU path)")
-        s = self._sampler
-        if s is None or B > s.cfg.max_batch or T > s.cfg.max_frames or s.device != dev or s._precision != self.precision:
-            if s is not None:
-                s.close()
-            s = self._make_sampler(max(B, s.cfg.max_batch if s is not None and s._precision == self.precision else 1), max(T, self.num_frames), dev)
-            s._precision = self.precision
-            self._sampler, self._dirty = s, True
-        if self._dirty:
-            s.load_state_dict(self._sampler_state())
-            s.prepare()
-            s._strategy = None
-            self._dirty = False
-        if s._strategy != self.sampling_strategy:
-            s.set_schedule(self.sampling_strategy, self.beta_scheduler, self.diffusion_steps)
-            s._strategy = self.sampling_strategy
-        return s
-
-    def _inputs(self, batch):
-        cond = batch["cond"]
-        B, T = cond.shape[0], int(batch["motion_lens"][0])
-        x_T = batch["x_T"] if batch.get("x_T") is not None else torch.randn(B, T, self.WIDTH, device=self.device)
-        if tuple(x_T.shape) != (B, T, self.WIDTH):
-            raise ValueError(f"{type(self).__name__}: x_T [{B}, {T}, {self.WIDTH}] expected, got {tuple(x_T.shape)}")
-        return cond, x_T, B, T
-
-    def _sample_many(self, batches, batching, max_rows, max_items, eta=0.0, skip_timesteps=0, options=True):
-        who = f"{type(self).__name__}.sample_many"
-        if batching not in ("sequential", "ragged"):
-            raise ValueError(f'{who}: batching {batching!r} not recognized ("ragged" or "sequential")')
-        eta, skip = float(eta), int(skip_timesteps)
-        if eta < 0:
-            raise ValueError(f"eta={eta} must be >= 0")
-        form, seeds = _loop_forms(batches, eta, who)
-        has = lambda k: any(b.get(k) is not None for b in batches)
-        use_opts = bool(eta or skip or has("x_start") or has("init_image"))
-        if use_opts and not options:
-            # the library decides: its refusal (mode 1 keeps the option refusals) comes back as NotImplementedError with its message
-            cond, x_T, B, T = self._inputs(batches[0])
-            _unsupported(self._get_sampler(B, T).sample, cond, x_T, eta=eta, skip_timesteps=skip, seed=seeds[0], x_start=batches[0].get("x_start"),
-                         init_image=batches[0].get("init_image"))
-            raise NotImplementedError(f"{who}: the loop options are not covered by this sampler")
-        if batching == "sequential":
-            out = []
-            for i, b in enumerate(batches):
-                kw = dict(eta=eta, skip_timesteps=skip, seed=seeds[i], step_noise=b.get("step_noise") if form == "noise" else None,
-                          x_start=b.get("x_start"), init_image=b.get("init_image")) if use_opts else {}
-                out.append({"output": self.forward(b, **kw)["output"]})
-            return out
-        ins = [self._inputs(b) for b in batches]
-        Bs, Ts = [v[2] for v in ins], [v[3] for v in ins]
-        motions = [(i, j) for i, nb in enumerate(Bs) for j in range(nb)]
-        groups, cur, rows = [], [], 0
-        for (i, j) in motions:
-            if cur and (rows + Ts[i] > max_rows or len(cur) >= max_items):
-                groups.append(cur)
-                cur, rows = [], 0
-            cur.append((i, j))
-            rows += Ts[i]
-        if cur:
-            groups.append(cur)
-        Tm = max(max(Ts), self.num_frames)
-        smp = self._get_sampler(max(max(len(g) for g in groups), -(-max(sum(Ts[i] for i, _ in g) for g in groups) // Tm)), Tm)
-        S = smp.schedule.num_timesteps
-        if not 0 <= skip < S:
-            raise ValueError(f"skip_timesteps={skip} outside [0, {S})")
-        steps = S - skip
-        if form == "noise":
-            for i, b in enumerate(batches):
-                sn = b["step_noise"]
-                if sn.dim() != 4 or sn.shape[0] < steps or tuple(sn.shape[1:]) != (Bs[i], Ts[i], self.WIDTH):
-                    raise ValueError(f"{who}: batch {i}: step_noise [>= {steps}, {Bs[i]}, {Ts[i]}, {self.WIDTH}] expected, got {tuple(sn.shape)}")
-        for k in ("x_start", "init_image"):
-            for i, b in enumerate(batches):
-                if b.get(k) is not None and (b[k].dim() != 3 or b[k].shape[0] != Bs[i]):
-                    raise ValueError(f"{who}: batch {i}: {k} [{Bs[i]}, T, {self.WIDTH}] expected, got {tuple(b[k].shape)}")
-        outs = [[None] * nb for nb in Bs]
-        pend = []
-        if eta:
-            smp.set_eta(eta)
-        try:
-            for g in groups:
-                kw = {}
-                if use_opts:
-                    kw["skip_timesteps"] = skip
-                    if form == "seed":
-                        kw["seeds"], kw["noise_rows"] = [seeds[i] for i, _ in g], [j for _, j in g]
-                    elif form == "noise":
-                        kw["noise"] = [batches[i]["step_noise"][:steps, j] for i, j in g]
-                    for k in ("x_start", "init_image"):
-                        if batches[g[0][0]].get(k) is not None:
-                            kw[k] = [batches[i][k][j] for i, j in g]
-                items, _, ev = smp.sample_ragged_async(torch.cat([ins[i][0][j:j + 1] for i, j in g], 0), [ins[i][1][j] for i, j in g], [Ts[i] for i, _ in g], **kw)
-                pend.append((g, items, ev))
-        finally:
-            if eta:
-                smp.set_eta(0.0)
-        for g, items, ev in pend:
-            ev.synchronize()
-            for (i, j), it in zip(g, items):
-                outs[i][j] = it
-        torch.cuda.current_stream(self.device).wait_stream(smp.stream)
-        return [{"output": torch.stack(o, 0)} for o in outs]
-
-
-    def invert(self, batch, steps=None):
-        """DDIM inversion of batch["motions"] [B, T, WIDTH] (normalised space) under batch["cond"] -> {"latent": [B, T, WIDTH], "steps": k}: the chain at
-        respaced step k (None = all S steps: the x_T of a plain forward).  For k < S, forward(dict(batch, x_T=latent), start_step=k) walks the same levels
-        down again."""
-        return _invert(self, batch, steps)
-
-    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
-        """invert for many batches with sample_many's packing: every latent bit-identical to that batch's own invert call."""
-        return _invert_many(self, batches, batching, steps, max_rows, max_items)
+    _with_cond = _text_all
 
 
 class InterDiffusion(_StandaloneDiffusion):
@@ -1227,7 +1164,7 @@ class InterDiffusion(_StandaloneDiffusion):
         return self._sample_many(batches, batching, max_rows, max_items, eta, skip_timesteps)
 
 
-class InterGen(nn.Module):
+class InterGen(_TextStage, nn.Module):
     """InterGen(cfg) facade (src/models/intergen.py:20-94) around InterDiffusion.  Checkpoint keys: ``decoder.net.*`` (the denoiser), the aliased CLIP tower
     ``token_embedding.* / positional_embedding / clip_transformer.* / ln_final.*`` and the text head ``clipTransEncoder.* / clip_ln.*``; a Lightning
     checkpoint {"state_dict": {"model.<key>": ...}} is unwrapped.  Text: when the checkpoint carries tower and head, ``text_process`` runs them on the GPU
@@ -1279,6 +1216,8 @@ class InterGen(nn.Module):
         batch[out_name] = head(tower(tok), tok)
         return batch
 
+    _with_cond = text_process
+
     def decode_motion(self, batch):
         batch.update(self.decoder(batch))
         return batch
@@ -1295,33 +1234,16 @@ class InterGen(nn.Module):
         batch.update(self.decoder(batch, **loop_kw))
         return batch
 
-    def invert(self, batch, steps=None):
-        """InterDiffusion.invert after text_process."""
-        with torch.no_grad():
-            batch = self.text_process(dict(batch))
-        return self.decoder.invert(batch, steps)
 
-    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
-        """InterDiffusion.invert_many after text_process."""
-        with torch.no_grad():
-            batches = [self.text_process(dict(b)) for b in batches]
-        return self.decoder.invert_many(batches, batching=batching, steps=steps, max_rows=max_rows, max_items=max_items)
-
-    def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
-        """InterDiffusion.sample_many after text_process; mode / inflight / keep_history are accepted for generate_for_evaluation's call and unused (one chain,
-        no history side outputs)."""
-        with torch.no_grad():
-            batches = [self.text_process(dict(b)) for b in batches]
-        return self.decoder.sample_many(batches, batching=batching, max_rows=max_rows, max_items=max_items, eta=eta, skip_timesteps=skip_timesteps)
-
-
-class MDM(_StandaloneDiffusion):
+class MDM(_TextStage, _StandaloneDiffusion):
     """MDM(cfg, num_frames, sampling_strategy) (src/models/mdm.py:9-66, 195-231): MDMDenoiser ``model`` under ClassifierFreeSampleModel(cfg.CFG_WEIGHT),
     one person, [B, T, 262]; runs on ``Sampler(single_only=1, model1_kind=1)`` -- precision "fp32" or "fp32_split", as the handle allows.  Parameters:
     ``model.*`` and ``embed_text.*``; text goes through MDM's own CLIP model + embed_text (mixermdm_amd.text.MdmTextHead) when the checkpoint carries
     ``clip_model.*``, else pass 'cond' [B, LATENT_DIM] (what embed_text hands the denoiser).  The loop options are refused by the library for this mode:
     NotImplementedError with its message."""
     WIDTH = 262
+    _loop_options = False
+    _sampler_model = property(lambda self: self)
 
     def __init__(self, cfg, num_frames=300, sampling_strategy="ddim50"):
         super().__init__()
@@ -1391,26 +1313,5 @@ class MDM(_StandaloneDiffusion):
         return self.forward(batch)
 
     def _with_cond(self, batch):
-        b = dict(batch)
-        with torch.no_grad():
-            b["cond"] = self.generate_cond(b)
-        return b
-
-    def invert(self, batch, steps=None):
-        """DDIM inversion of batch["motions"] [B, T, 262] under the batch's text / 'cond' -> {"latent": [B, T, 262], "steps": k}."""
-        return _invert(self, self._with_cond(batch), steps)
-
-    def invert_many(self, batches, batching="ragged", steps=None, max_rows=4800, max_items=64):
-        """invert for many batches over the ragged path of the single-person sampler (its token-row maps), bit-identical to the sequential calls."""
-        return _invert_many(self, [self._with_cond(b) for b in batches], batching, steps, max_rows, max_items)
-
-    def sample_many(self, batches, mode=None, batching="ragged", inflight=None, max_rows=4800, max_items=64, keep_history=None, *, eta=0.0, skip_timesteps=0):
-        """Many forward calls at once over the ragged path of the single-person sampler -> one {"output": [b, T, 262]} per batch, bit-identical to the
-        sequential calls.  eta / skip_timesteps or loop arguments in the batch dicts: NotImplementedError (the library's message)."""
-        with torch.no_grad():
-            bs = []
-            for b in batches:
-                b = dict(b)
-                b["cond"] = self.generate_cond(b)
-                bs.append(b)
-        return self._sample_many(bs, batching, max_rows, max_items, eta, skip_timesteps, options=False)
+        batch["cond"] = self.generate_cond(batch)
+        return batch

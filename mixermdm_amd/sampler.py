@@ -247,6 +247,19 @@ class Sampler:
         self.eta = 0.0
         return sch
 
+    def use_schedule(self, sch):
+        """The handle on the schedule OBJECT `sch` (a facade builds a new one per call), compared by CONTENT: the tables are uploaded, the time-embedding
+        tables rebuilt and eta reset to 0 only when sch.key() differs from what the handle holds, so that nothing is re-captured through the (B, T, S)
+        graph cache.  (The upload is set_schedule's, which is left as it stands: see DESIGN.md section 9g.)"""
+        if self._strategy != sch.key():
+            tmap = np.ascontiguousarray(np.array(sch.timestep_map, dtype=np.int32))
+            coef = np.ascontiguousarray(sch.device_coefficients())
+            with torch.cuda.device(self.device):
+                check(self.lib.mmdm_set_schedule(self.h, tmap.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p), sch.num_timesteps, self._s()), self.h)
+            self.schedule, self._strategy = sch, sch.key()
+            self.eta = 0.0                                 # the upload resets the handle's eta table
+        return sch
+
     def set_eta(self, eta):
         """mmdm_set_eta: the stochastic DDIM family (gaussian_diffusion.py:1939-1963), eta = 1 being DDPM-like.  Call after set_schedule (which resets
         it to 0).  While eta > 0 every begin / sample names a noise source (noise= or seed=); eta = 0 clears the table."""
