@@ -48,7 +48,7 @@ NO_PACKED_FP32_OBJECTS = [u[1] for u in UNITS if "-packed-fp32-ops" in u[2]]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden"]
 
 
-SHA_FILES = {"fp32": ("gemm_f32.hip", "mmdm.hip", "kernels.h"), "fp32_split": ("gemm_split.hip", "mmdm.hip", "kernels.h"),
+SHA_FILES = {"fp32": ("gemm_f32.hip", "gemm_f32_plan.h", "mmdm.hip", "kernels.h"), "fp32_split": ("gemm_split.hip", "mmdm.hip", "kernels.h"),
              "bf16": ("gemm_bf16.hip", "mmdm.hip", "kernels.h"), "bf16_fp8": ("gemm_bf16.hip", "gemm_fp8p.hip", "gemm_fp8p.h", "mmdm.hip", "kernels.h")}
 
 _COMMENT_OR_STRING = re.compile(r'//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\\n])*"|\'(?:\\.|[^\'\\\n])*\'', re.S)

@@ -3,10 +3,12 @@
 // Replaces torch.nn.functional.linear at every call site of the denoising path (SURVEY.md 2.3 K1,K2,K4,K6,K7,K8;
 // reference: src/models/utils/layers.py:33-34,74-75,99-106,109-116, src/models/in2in.py:389-390,426-431).
 //
+// Which kernel a call runs is decided in gemm_f32_plan.h (a pure host function, tested on the CPU); this file holds the kernels and one
+// launcher per kernel form.  First the register-staged fallback, gemm_f32_kernel (K % 16 != 0 or a misaligned A / W):
 // Tiling (64-wide wavefronts): 128x128 output tile per 256-thread workgroup, 4 waves as 2(M) x 2(N), each wave
-// 64x64 = 2x2 MFMA tiles of 32x32 (64 accumulator registers).  K is walked in steps of 32 through a
-// double-buffered LDS image; rows are padded to 36 floats so that every ds_read_b128 lane group touches 16
-// distinct 16-byte bank slots (36*i mod 64 is a distinct multiple of 4 for 16 distinct i mod 16).
+// 64x64 = 2x2 MFMA tiles of 32x32 (64 accumulator registers).  K is walked in steps of 16 through a
+// double-buffered LDS image; rows are padded to 20 floats so that every ds_read_b128 lane group touches 16
+// distinct 16-byte bank slots (20*i mod 64 is a distinct multiple of 4 for 16 distinct i mod 16).
 // K order inside a step is permuted identically for both operands (lane half h supplies k = 8g + 4h + s for MFMA
 // s = 0..3 of group g), which lets each lane fetch its four operands for four MFMAs with one 16-byte LDS read.
 // Global->LDS staging is register-staged (global_load_dwordx4 -> ds_write_b128): the padded image rules out LDS-DMA.
@@ -16,6 +18,7 @@
 #include <string.h>
 #include <type_traits>
 #include "kernels.h"
+#include "gemm_f32_plan.h"
 
 namespace {
 
@@ -28,8 +31,7 @@ struct GemmArgs {
     int lda, ldw, ldc, ld_extra;
     int M, N, K, Kw, epilogue, period;   // Kw >= K: readable columns of W (zero beyond K)
     int mt, nt;
-    int ablate;                          // timing experiments only (tools/gemm_bench.py); 0 in production
-    unsigned long long* stamps;          // diagnostic builds of a launch only (tools/gemm_timeline.py): per-workgroup {start, loop start, loop end, placement, kernel end, kernel entry, residual landed, stores issued}, then {s_memtime at loop start, loop end} per workgroup
+    unsigned long long* stamps;          // stamping twin of a launch only (tools/gemm_timeline.py): per-workgroup {start, loop start, loop end, placement, kernel end, kernel entry, residual landed, stores issued}, then {s_memtime at loop start, loop end} per workgroup
                                          // in 100 MHz s_memrealtime ticks; nullptr in production (one never-taken scalar branch per workgroup)
 };
 
@@ -133,15 +135,15 @@ __global__ __launch_bounds__((Cfg<TM_, TN_, BK_>::THREADS)) void gemm_f32_kernel
     for (int kt = 0; kt < nkt; ++kt) {
         const int cur = kt & 1;
         const bool more = (kt + 1) < nkt;
-        if (more && p.ablate < 1) {
+        if (more) {
             const int k0 = (kt + 1) * BK + sc;
 #pragma unroll
             for (int j = 0; j < C_::PA; ++j) ra[j] = load4<AVEC, FULL>(p.A, p.lda, m0 + sr + C_::ROWS_PER_PASS * j, p.M, k0, p.K);
 #pragma unroll
             for (int j = 0; j < C_::PB; ++j) rb[j] = load4<WVEC, FULL>(p.W, p.ldw, n0 + sr + C_::ROWS_PER_PASS * j, p.N, k0, p.Kw);
         }
-        const float* Ac = As + (p.ablate >= 1 ? 0 : cur) * C_::A_FLOATS + a_off;
-        const float* Bc = Bs + (p.ablate >= 1 ? 0 : cur) * C_::B_FLOATS + b_off;
+        const float* Ac = As + cur * C_::A_FLOATS + a_off;
+        const float* Bc = Bs + cur * C_::B_FLOATS + b_off;
         // fragments of group g+1 are fetched before the MFMAs of group g (register double buffering)
         f32x4 af[2][TM], bf[2][TN];
 #pragma unroll
@@ -165,7 +167,7 @@ __global__ __launch_bounds__((Cfg<TM_, TN_, BK_>::THREADS)) void gemm_f32_kernel
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cb][i][s], bf[cb][j][s], acc[i][j], 0, 0, 0);
         }
-        if (more && p.ablate < 1) {
+        if (more) {
             float* An = As + (cur ^ 1) * C_::A_FLOATS;
             float* Bn = Bs + (cur ^ 1) * C_::B_FLOATS;
 #pragma unroll
@@ -173,7 +175,7 @@ __global__ __launch_bounds__((Cfg<TM_, TN_, BK_>::THREADS)) void gemm_f32_kernel
 #pragma unroll
             for (int j = 0; j < C_::PB; ++j) *reinterpret_cast<f32x4*>(&Bn[(sr + C_::ROWS_PER_PASS * j) * LDP + sc]) = rb[j];
         }
-        if (p.ablate < 2) __syncthreads();
+        __syncthreads();
     }
 
     // epilogue: C/D map of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
@@ -231,11 +233,10 @@ template <int CPR> __device__ __forceinline__ int swz_of(int r) { return CPR == 
 // VEPI: the MFMA operands are swapped (D^T = W A^T), which puts the output ROW on the lane and four consecutive output
 // COLUMNS in consecutive accumulator registers -- bias / residual / PE loads and the result stores are then 16-byte
 // accesses (4x fewer memory instructions than the one-float-per-lane map).  Needs N % 4 == 0 and 16-byte aligned C / extra rows.
-// MINW_: minimum waves per SIMD the register allocation must allow (second __launch_bounds__ argument; 1 = no constraint).  The 64
-// accumulator registers of a 64x64 wave tile plus operands, addresses and the accumulator-initialisation transients come to ~144
-// registers when unconstrained (3 waves per SIMD = THREE 4-wave workgroups per CU); MINW_ = 5 makes the compiler fit 96.
+// The register allocation is unconstrained (second __launch_bounds__ argument 1): the 64 accumulator registers of a 64x64 wave tile plus
+// operands, addresses and the accumulator-initialisation transients come to ~144 registers (3 waves per SIMD = THREE 4-wave workgroups per CU).
 //
-// PIPE_ = 1: software-pipelined K loop for NBUF_ >= 3 stages (the production loop).  The 2-stage loop above it makes every K step pay
+// PIPE_: software-pipelined K loop for NBUF_ >= 3 stages (the production loop).  The 2-stage loop above it makes every K step pay
 // its own latencies in sequence -- vmcnt(0) on a tile issued only one step (2048 MFMA cycles) earlier, the barrier, the LDS-DMA issue
 // of the next tile, then the fragment reads -- before its first MFMA can issue: a workgroup alone on a CU reaches ~70 % of the MFMA rate
 // and the kernel depends on co-resident workgroups to fill the holes (three fit: 144 registers; tools/gemm_timeline.py).  Here
@@ -252,15 +253,13 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 // One output tile (`swz` = tile index after the XCD remap) from start to finish.  Device pass only: the buffer-resource type of the
 // LDS-DMA builtins does not exist in the host pass, which only needs the kernel's symbol.
 #if defined(__HIP_DEVICE_COMPILE__)
-// DIAG_: the timing ablations (GemmArgs::ablate) and in-kernel stamps (GemmArgs::stamps) exist in a second instantiation only, launched
-// when a tool has set one of them (tools/gemm_bench.py ABL=, tools/gemm_timeline.py, bench.py's loop clock); the production instantiation
-// sees compile-time zeros -- no diagnostic branch, load or register in the shipped kernels.
-template <int TM_, int TN_, int BK_, int NBUF_, bool VEPI, int PIPE_, bool DIAG_>
-__device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int swz, int bid) {
+// DIAG_: the in-kernel stamps (GemmArgs::stamps) exist in a second instantiation only, the stamping twin, launched when a tool has set
+// them (tools/gemm_timeline.py, bench.py's loop clock); the production instantiation sees a compile-time null -- no diagnostic branch,
+// load or register in the shipped kernels.
+template <int TM_, int TN_, int BK_, int NBUF_, bool VEPI, bool PIPE_, bool DIAG_>
+__device__ __forceinline__ void gemm_tile(const GemmArgs& p, float* smem, int swz, int bid) {
     using C_ = GCfg<TM_, TN_, BK_, NBUF_>;
-    const GemmArgs& p = pp;
-    unsigned long long* const p_stamps = DIAG_ ? pp.stamps : nullptr;
-    const int p_ablate = DIAG_ ? pp.ablate : 0;
+    unsigned long long* const p_stamps = DIAG_ ? p.stamps : nullptr;
     constexpr int BM = C_::BM, BN = C_::BN, BK = C_::BK, TM = C_::TM, TN = C_::TN, CPR = C_::CPR, RPP = C_::RPP, NBUF = C_::NBUF;
     float* As = smem;                                   // [NBUF][BM*BK]
     float* Bs = smem + NBUF * C_::A_FLOATS;             // [NBUF][BN*BK]
@@ -325,7 +324,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
     // reference's `x + linear(...)` -- so a workgroup's first MFMA waits for one 16 KB operand tile instead of 64 KB of residual plus
     // NBUF-1 tiles (13-19 us of every workgroup's life, and of every kernel's start, in the round-1 kernel).  Every pipelined
     // instantiation uses this order, so a row's result does not depend on the tile shape that produced it.
-    constexpr bool LATE_R = PIPE_ != 0 && VEPI;
+    constexpr bool LATE_R = PIPE_ && VEPI;
     // accumulators start as bias (+ residual / + PE row unless LATE_R)
     f32x16 acc[TM][TN];
     if (VEPI) {
@@ -372,7 +371,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
         }
     }
 
-    if constexpr (PIPE_ != 0) {
+    if constexpr (PIPE_) {
         // The first NBUF-1 operand tiles are requested behind the accumulator-initialisation loads; vmcnt retires in order, so
         // "at most the NBUF-2 newest tiles outstanding" means the initialisation values and tile 0 have landed: the loop starts on
         // tile 0 while the others are still on their way (the host side guarantees nkt >= NBUF).
@@ -393,7 +392,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
     const int b_row = (wn * (32 * TN) + l31) * BK;
 
     f32x4 rv[LATE_R ? TM : 1][LATE_R ? TN : 1][4];               // the late residual tile (LATE_R only)
-    if constexpr (PIPE_ != 0) {
+    if constexpr (PIPE_) {
         static_assert((C_::G == 2 || C_::G == 4) && NBUF >= 3 && NBUF <= 6, "pipelined loop: K step 16 or 32 (two / four k-groups), 3 to 6 stages");
         static_assert((C_::NI + 1) / 2 <= 4 * TM * TN - 1, "LDS-DMA pieces of a tile must fit behind the MFMAs of two k-groups");
         constexpr int NI = C_::NI;
@@ -441,26 +440,26 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
             constexpr bool STG = decltype(do_stage)::value;
             // the pieces of the tile being requested are split over k-groups 0 and 1 (tools/loop_bench3.hip: 2 + 2 beats 4 + 0)
             constexpr int D0 = (NI + 1) / 2, D1 = NI - D0;
-            constexpr int dma_here = (!STG || PIPE_ == 2) ? 0 : (g == 0 ? D0 : (g == 1 ? D1 : 0));
+            constexpr int dma_here = !STG ? 0 : (g == 0 ? D0 : (g == 1 ? D1 : 0));
             constexpr int before_wait = G == 2 ? D0 : NI;      // pieces of the newest tile already issued when the step's wait executes
             if constexpr (g == G - 1) {
                 if (more) {
                     if constexpr (STG) wait_vm<(NBUF - 3) * NI + before_wait>();      // tile kt+1 landed; tiles kt+2 .. may be in flight
                     else wait_left(left);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if constexpr (PIPE_ != 3) __builtin_amdgcn_s_barrier();      // PIPE_ 2 / 3: timing ablations (tools/gemm_bench.py), wrong results
+                    __builtin_amdgcn_s_barrier();
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             if constexpr (g % 2 == 0) {
                 if constexpr (g < G - 1) rd(cur, g + 1, a1, b1);
                 else if (more) rd(nxt, 0, a1, b1);
-                if constexpr (STG && g == 0 && PIPE_ != 2) stage_part(stg, std::integral_constant<int, 0>{}, std::integral_constant<int, D0>{});
+                if constexpr (STG && g == 0) stage_part(stg, std::integral_constant<int, 0>{}, std::integral_constant<int, D0>{});
                 mm(a0, b0);
             } else {
                 if constexpr (g < G - 1) rd(cur, g + 1, a0, b0);
                 else if (more) rd(nxt, 0, a0, b0);
-                if constexpr (STG && g == 1 && PIPE_ != 2) stage_part(stg, std::integral_constant<int, D0>{}, std::integral_constant<int, NI>{});
+                if constexpr (STG && g == 1) stage_part(stg, std::integral_constant<int, D0>{}, std::integral_constant<int, NI>{});
                 mm(a1, b1);
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 1, g);
@@ -505,25 +504,15 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
         for (int kt = n_main < 0 ? 0 : n_main; kt < nkt; ++kt)           // drain: no new tile
             step(std::false_type{}, nkt - kt - 2, kt + 1 < nkt);
     } else {
+    static_assert(NBUF == 2, "the 2-stage loop");
     stage(0);
-    if (NBUF == 3 && nkt > 1) stage(1);
     for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = NBUF == 3 ? kt % 3 : (kt & 1);
-        if (NBUF == 3) {
-            // tile kt has landed once at most the NI loads of tile kt+1 are still in flight
-            if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C_::NI) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            // raw barrier: __syncthreads() would drain vmcnt(0) while LDS-DMA is in flight and serialise the pipeline
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                      // everyone done reading buffer (kt+2)%3 (tile kt-1)
-            if (kt + 2 < nkt && (p_ablate & 7) < 1) stage((kt + 2) % 3);
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (kt + 1 < nkt && (p_ablate & 7) < 1) stage(cur ^ 1);
-        }
-        const float* Ac = As + ((p_ablate & 7) >= 1 ? 0 : cur) * C_::A_FLOATS + a_row;
-        const float* Bc = Bs + ((p_ablate & 7) >= 1 ? 0 : cur) * C_::B_FLOATS + b_row;
+        const int cur = kt & 1;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (kt + 1 < nkt) stage(cur ^ 1);
+        const float* Ac = As + cur * C_::A_FLOATS + a_row;
+        const float* Bc = Bs + cur * C_::B_FLOATS + b_row;
 #pragma unroll
         for (int g = 0; g < C_::G; ++g) {
             const int cg = 4 * ((2 * g + lh) ^ sw);
@@ -532,7 +521,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
             for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(Ac + i * 32 * BK + cg);
 #pragma unroll
             for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Bc + j * 32 * BK + cg);
-            if (p_ablate & 8) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -541,11 +529,9 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = VEPI ? __builtin_amdgcn_mfma_f32_32x32x2f32(bf[j][s], af[i][s], acc[i][j], 0, 0, 0)
                                          : __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][s], bf[j][s], acc[i][j], 0, 0, 0);
-            if (p_ablate & 8) __builtin_amdgcn_s_setprio(0);
         }
     }
     }
-    if ((p_ablate & 7) >= 3) return;
     // MFMA -> VALU hazard across the loop-exit branch: see MFMA_SETTLE in attn_f32.hip
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -638,8 +624,8 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& pp, float* smem, int s
 }
 #endif
 
-template <int TM_, int TN_, int BK_, int NBUF_, bool VEPI, int MINW_ = 1, int PIPE_ = 0, bool DIAG_ = false>
-__global__ __launch_bounds__((GCfg<TM_, TN_, BK_, NBUF_>::THREADS), MINW_) void gemm_glds_kernel(GemmArgs p) {
+template <int TM_, int TN_, int BK_, int NBUF_, bool VEPI, bool PIPE_, bool DIAG_>
+__global__ __launch_bounds__((GCfg<TM_, TN_, BK_, NBUF_>::THREADS), 1) void gemm_glds_kernel(GemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int nwg = p.mt * p.nt;
@@ -850,210 +836,149 @@ __global__ __launch_bounds__(256) void gemm_mix_kernel(MixArgs q) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int bid = blockIdx.x;
-    if (bid < q.n_main) gemm_tile<21, 21, 16, 4, VEPI, 1, false>(q.main, smem, xcd_swz(bid, q.n_main), bid);
+    if (bid < q.n_main) gemm_tile<21, 21, 16, 4, VEPI, true, false>(q.main, smem, xcd_swz(bid, q.n_main), bid);
     else s16_tile<1, 4, VEPI>(q.rem, smem, xcd_swz(bid - q.n_main, q.rem.mt * q.rem.nt));
 #endif
 }
 
-// what the 16-byte accesses of gemm_s16_kernel need (every epilogue: bias quads, result quads; residual / PE rows)
-inline bool s16_ok(const GemmArgs& a) {
-    const bool ext = a.epilogue == MMDM_EPI_BIAS_RESID || a.epilogue == MMDM_EPI_BIAS_PE;
-    return (a.N & 3) == 0 && (a.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0 && (a.K & 31) == 0 && a.Kw == a.K &&
-           (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0) &&
-           (!ext || ((a.ld_extra & 3) == 0 && (reinterpret_cast<uintptr_t>(a.extra) & 15) == 0));
+// Host half.  gemm_f32_plan.h decides which kernel forms a call launches; here one launcher (and one attribute registration) per form.
+namespace P = gemm_f32_plan;
+
+int set_smem(const void* const* fns, int n, int bytes, const char* what) {
+    for (int i = 0; i < n; ++i) {
+        hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return mmdm_set_error(MMDM_ERR_HIP, "hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
+    }
+    return MMDM_OK;
+}
+#define KFN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+
+// the register-staged fallback: its load form follows the operands (16-byte or scalar loads per operand; FULL: no edge in M, N or K)
+template <int AVEC, int WVEC, bool FULL>
+int launch_f32_form(GemmArgs a, hipStream_t st) {
+    using C_ = Cfg<22, 22, 16>;
+    a.mt = (a.M + C_::BM - 1) / C_::BM;
+    a.nt = (a.N + C_::BN - 1) / C_::BN;
+    hipLaunchKernelGGL((gemm_f32_kernel<22, 22, 16, AVEC, WVEC, FULL>), dim3(a.mt * a.nt), dim3(C_::THREADS), C_::SMEM_BYTES, st, a);
+    return mmdm_check_launch("gemm_f32");
+}
+int launch_f32(GemmArgs a, const P::Call& c, const P::Launch&, hipStream_t st) {
+    using C_ = Cfg<22, 22, 16>;
+    const bool av = P::a_vec4(c), wv = P::w_vec4(c);
+    if (av && wv && a.M % C_::BM == 0 && a.N % C_::BN == 0 && a.K % C_::BK == 0 && a.Kw == a.K) return launch_f32_form<4, 4, true>(a, st);
+    if (av && wv) return launch_f32_form<4, 4, false>(a, st);
+    if (wv) return launch_f32_form<1, 4, false>(a, st);
+    if (av) return launch_f32_form<4, 1, false>(a, st);
+    return launch_f32_form<1, 1, false>(a, st);
+}
+int attr_f32() {
+    const void* fns[] = {KFN(gemm_f32_kernel<22, 22, 16, 4, 4, true>), KFN(gemm_f32_kernel<22, 22, 16, 4, 4, false>), KFN(gemm_f32_kernel<22, 22, 16, 1, 4, false>),
+                         KFN(gemm_f32_kernel<22, 22, 16, 4, 1, false>), KFN(gemm_f32_kernel<22, 22, 16, 1, 1, false>)};
+    return set_smem(fns, 5, Cfg<22, 22, 16>::SMEM_BYTES, "gemm");
 }
 
-template <int TN16_, int NBUF_>
-int launch_s16(GemmArgs a, hipStream_t st) {
+// 2-stage and pipelined LDS-DMA kernels; a stamp buffer (a tool's, bench.py's loop clock) selects the stamping twin
+template <int TM_, int TN_, int NBUF_, bool PIPE_, bool VEPI>
+int launch_glds(GemmArgs a, const P::Call&, const P::Launch&, hipStream_t st) {
+    using C_ = GCfg<TM_, TN_, 16, NBUF_>;
+    a.mt = (a.M + C_::BM - 1) / C_::BM;
+    a.nt = (a.N + C_::BN - 1) / C_::BN;
+    const dim3 grid(a.mt * a.nt), block(C_::THREADS);
+    if (a.stamps) hipLaunchKernelGGL((gemm_glds_kernel<TM_, TN_, 16, NBUF_, VEPI, PIPE_, true>), grid, block, C_::SMEM_BYTES, st, a);
+    else hipLaunchKernelGGL((gemm_glds_kernel<TM_, TN_, 16, NBUF_, VEPI, PIPE_, false>), grid, block, C_::SMEM_BYTES, st, a);
+    return mmdm_check_launch("gemm_glds");
+}
+template <int TM_, int TN_, int NBUF_, bool PIPE_, bool VEPI>
+int attr_glds() {
+    const void* fns[] = {KFN(gemm_glds_kernel<TM_, TN_, 16, NBUF_, VEPI, PIPE_, false>), KFN(gemm_glds_kernel<TM_, TN_, 16, NBUF_, VEPI, PIPE_, true>)};
+    return set_smem(fns, 2, GCfg<TM_, TN_, 16, NBUF_>::SMEM_BYTES, "gemm_glds");
+}
+
+template <int TN16_, int NBUF_, bool LATE>
+int launch_s16(GemmArgs a, const P::Call&, const P::Launch&, hipStream_t st) {
     using C_ = S16Cfg<TN16_, NBUF_>;
     a.mt = (a.M + C_::BM - 1) / C_::BM;
     a.nt = (a.N + C_::BN - 1) / C_::BN;
-    const bool late = a.epilogue == MMDM_EPI_BIAS_RESID || a.epilogue == MMDM_EPI_BIAS_PE;
-    mmdm_note_gemm("gemm_s16<%d,%d,%s>", TN16_, NBUF_, late ? "late" : "plain");
-    const dim3 grid(a.mt * a.nt), block(C_::THREADS);
-    if (late) hipLaunchKernelGGL((gemm_s16_kernel<TN16_, NBUF_, true>), grid, block, C_::SMEM_BYTES, st, a);
-    else hipLaunchKernelGGL((gemm_s16_kernel<TN16_, NBUF_, false>), grid, block, C_::SMEM_BYTES, st, a);
+    hipLaunchKernelGGL((gemm_s16_kernel<TN16_, NBUF_, LATE>), dim3(a.mt * a.nt), dim3(C_::THREADS), C_::SMEM_BYTES, st, a);
     return mmdm_check_launch("gemm_s16");
 }
+template <int TN16_, int NBUF_, bool LATE>
+int attr_s16() { const void* fns[] = {KFN(gemm_s16_kernel<TN16_, NBUF_, LATE>)}; return set_smem(fns, 1, S16Cfg<TN16_, NBUF_>::SMEM_BYTES, "gemm_s16"); }
 
-// rows [0, M1) on 64 x 64 tiles, rows [M1, M) on the 16 x 16-chain tiles, one launch (a.epilogue != PE: the row index restarts in the remainder)
-int launch_mix(const GemmArgs& a, int M1, hipStream_t st) {
+// rows [0, M1) on 64 x 64 tiles, rows [M1, M) on the 16 x 16-chain tiles, one launch (never the PE epilogue: the row index restarts in the remainder)
+template <bool VEPI>
+int launch_mix(GemmArgs a, const P::Call&, const P::Launch& l, hipStream_t st) {
     using CM = GCfg<21, 21, 16, 4>;
     using CR = S16Cfg<1, 4>;
     static_assert(CM::SMEM_BYTES == CR::SMEM_BYTES && CM::THREADS == CR::THREADS, "the two tile forms share one launch configuration");
     MixArgs q;
     q.main = a; q.rem = a;
-    q.main.M = M1;
-    q.rem.M = a.M - M1;
-    q.rem.A = a.A + (size_t)M1 * a.lda;
-    q.rem.C = a.C + (size_t)M1 * a.ldc;
-    if (a.extra) q.rem.extra = a.extra + (size_t)M1 * a.ld_extra;
-    q.main.mt = (M1 + CM::BM - 1) / CM::BM; q.main.nt = (a.N + CM::BN - 1) / CM::BN;
+    q.main.M = l.M1;
+    q.rem.M = a.M - l.M1;
+    q.rem.A = a.A + (size_t)l.M1 * a.lda;
+    q.rem.C = a.C + (size_t)l.M1 * a.ldc;
+    if (a.extra) q.rem.extra = a.extra + (size_t)l.M1 * a.ld_extra;
+    q.main.mt = (l.M1 + CM::BM - 1) / CM::BM; q.main.nt = (a.N + CM::BN - 1) / CM::BN;
     q.rem.mt = (q.rem.M + CR::BM - 1) / CR::BM; q.rem.nt = (a.N + CR::BN - 1) / CR::BN;
-    q.main.ablate = q.rem.ablate = 0; q.main.stamps = q.rem.stamps = nullptr;
+    q.main.stamps = q.rem.stamps = nullptr;
     q.n_main = q.main.mt * q.main.nt;
-    const bool ext = a.epilogue == MMDM_EPI_BIAS_RESID;
-    mmdm_note_gemm("gemm_mix<%s,%d+%d>", ext ? "vepi" : "scalar", q.n_main, q.rem.mt * q.rem.nt);
-    const dim3 grid(q.n_main + q.rem.mt * q.rem.nt), block(CM::THREADS);
-    if (ext) hipLaunchKernelGGL((gemm_mix_kernel<true>), grid, block, CM::SMEM_BYTES, st, q);
-    else hipLaunchKernelGGL((gemm_mix_kernel<false>), grid, block, CM::SMEM_BYTES, st, q);
+    hipLaunchKernelGGL((gemm_mix_kernel<VEPI>), dim3(q.n_main + q.rem.mt * q.rem.nt), dim3(CM::THREADS), CM::SMEM_BYTES, st, q);
     return mmdm_check_launch("gemm_mix");
 }
+template <bool VEPI>
+int attr_mix() { const void* fns[] = {KFN(gemm_mix_kernel<VEPI>)}; return set_smem(fns, 1, GCfg<21, 21, 16, 4>::SMEM_BYTES, "gemm_mix"); }
+#undef KFN
 
-int set_attr_mix() {
-    const void* fns[2] = {reinterpret_cast<const void*>(&gemm_mix_kernel<true>), reinterpret_cast<const void*>(&gemm_mix_kernel<false>)};
-    for (const void* f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, GCfg<21, 21, 16, 4>::SMEM_BYTES);
-        if (e != hipSuccess) return mmdm_set_error(MMDM_ERR_HIP, "hipFuncSetAttribute(gemm_mix): %s", hipGetErrorString(e));
-    }
-    return MMDM_OK;
+// The one table from a plan's kernel identifier to its code, in the order of gemm_f32_plan.h's list: what mmdm_linear_f32_ex launches and
+// what mmdm_gemm_init registers, so a kernel cannot be launchable without being registered.
+struct Form {
+    P::Kernel id;
+    int (*launch)(GemmArgs, const P::Call&, const P::Launch&, hipStream_t);
+    int (*attr)();
+};
+#define GLDS(id, ...) {P::id, launch_glds<__VA_ARGS__, false>, attr_glds<__VA_ARGS__, false>}, {P::id##_V, launch_glds<__VA_ARGS__, true>, attr_glds<__VA_ARGS__, true>}
+#define S16(id, ...) {P::id, launch_s16<__VA_ARGS__, false>, attr_s16<__VA_ARGS__, false>}, {P::id##_L, launch_s16<__VA_ARGS__, true>, attr_s16<__VA_ARGS__, true>}
+constexpr Form FORMS[] = {
+    {P::F32, launch_f32, attr_f32},
+    GLDS(GLDS_2221, 22, 21, 2, false), GLDS(GLDS_2222, 22, 22, 2, false),
+    GLDS(PIPE_2121, 21, 21, 4, true), GLDS(PIPE_2221, 22, 21, 4, true), GLDS(PIPE_2222, 22, 22, 5, true),
+    S16(S16_13, 1, 3), S16(S16_23, 2, 3), S16(S16_14, 1, 4), S16(S16_24, 2, 4),
+    {P::MIX, launch_mix<false>, attr_mix<false>}, {P::MIX_V, launch_mix<true>, attr_mix<true>},
+};
+#undef GLDS
+#undef S16
+constexpr bool forms_in_order() {
+    for (int i = 0; i < P::KERNEL_COUNT; ++i)
+        if (FORMS[i].id != i) return false;
+    return true;
 }
+static_assert(sizeof(FORMS) / sizeof(FORMS[0]) == P::KERNEL_COUNT && forms_in_order(), "one launcher per kernel of the plan, in the plan's order");
 
-template <int TN16_, int NBUF_>
-int set_attr_s16() {
-    constexpr int bytes = S16Cfg<TN16_, NBUF_>::SMEM_BYTES;
-    const void* fns[2] = {reinterpret_cast<const void*>(&gemm_s16_kernel<TN16_, NBUF_, true>), reinterpret_cast<const void*>(&gemm_s16_kernel<TN16_, NBUF_, false>)};
-    for (const void* f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return mmdm_set_error(MMDM_ERR_HIP, "hipFuncSetAttribute(gemm_s16): %s", hipGetErrorString(e));
-    }
-    return MMDM_OK;
-}
-
-inline bool vepi_ok(const GemmArgs& a) {
-    const bool ext = a.epilogue == MMDM_EPI_BIAS_RESID || a.epilogue == MMDM_EPI_BIAS_PE;
-    return (a.N & 3) == 0 && (a.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0 &&
-           (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0) &&
-           (!ext || ((a.ld_extra & 3) == 0 && (reinterpret_cast<uintptr_t>(a.extra) & 15) == 0));
-}
-
-template <int TM_, int TN_, int BK_ = 16, int NBUF_ = 2, int MINW_ = 1, int PIPE_ = 0>
-int launch_glds(GemmArgs a, hipStream_t st) {
-    using C_ = GCfg<TM_, TN_, BK_, NBUF_>;
-    a.mt = (a.M + C_::BM - 1) / C_::BM;
-    a.nt = (a.N + C_::BN - 1) / C_::BN;
-    // measured (tools/gemm_bench.py): the 16-byte epilogue pays where the accumulators are initialised from memory (+10 % on
-    // the K = 1024 residual GEMMs) and is neutral-to-slightly-negative for bias/GELU-only epilogues
-    const bool ext = a.epilogue == MMDM_EPI_BIAS_RESID || a.epilogue == MMDM_EPI_BIAS_PE;
-    const bool vepi = ext && vepi_ok(a) && !(a.ablate & 16);
-    const dim3 grid(a.mt * a.nt), block(C_::THREADS);
-    mmdm_note_gemm("%s<%d,%d,%d,%d,%s>", PIPE_ ? "gemm_pipe" : "gemm_glds", TM_, TN_, BK_, NBUF_, vepi ? "vepi" : "scalar");
-    if ((a.ablate & ~16) || a.stamps) {              // a tool asked for ablation bits / stamps: the diagnostic instantiation
-        if (vepi) hipLaunchKernelGGL((gemm_glds_kernel<TM_, TN_, BK_, NBUF_, true, MINW_, PIPE_, true>), grid, block, C_::SMEM_BYTES, st, a);
-        else hipLaunchKernelGGL((gemm_glds_kernel<TM_, TN_, BK_, NBUF_, false, MINW_, PIPE_, true>), grid, block, C_::SMEM_BYTES, st, a);
-    } else if (vepi)
-        hipLaunchKernelGGL((gemm_glds_kernel<TM_, TN_, BK_, NBUF_, true, MINW_, PIPE_, false>), grid, block, C_::SMEM_BYTES, st, a);
-    else
-        hipLaunchKernelGGL((gemm_glds_kernel<TM_, TN_, BK_, NBUF_, false, MINW_, PIPE_, false>), grid, block, C_::SMEM_BYTES, st, a);
-    return mmdm_check_launch("gemm_glds");
-}
-
-template <int TM_, int TN_, int BK_ = 16, int NBUF_ = 2, int MINW_ = 1, int PIPE_ = 0>
-int set_attr_glds() {
-    constexpr int bytes = GCfg<TM_, TN_, BK_, NBUF_>::SMEM_BYTES;
-    const void* fns[4] = {reinterpret_cast<const void*>(&gemm_glds_kernel<TM_, TN_, BK_, NBUF_, true, MINW_, PIPE_, false>),
-                          reinterpret_cast<const void*>(&gemm_glds_kernel<TM_, TN_, BK_, NBUF_, false, MINW_, PIPE_, false>),
-                          reinterpret_cast<const void*>(&gemm_glds_kernel<TM_, TN_, BK_, NBUF_, true, MINW_, PIPE_, true>),
-                          reinterpret_cast<const void*>(&gemm_glds_kernel<TM_, TN_, BK_, NBUF_, false, MINW_, PIPE_, true>)};
-    for (const void* f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return mmdm_set_error(MMDM_ERR_HIP, "hipFuncSetAttribute(gemm_glds): %s", hipGetErrorString(e));
-    }
-    return MMDM_OK;
-}
-
-template <int TM, int TN, int BK, int AVEC, int WVEC, bool FULL>
-int set_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<TM, TN, BK, AVEC, WVEC, FULL>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<TM, TN, BK>::SMEM_BYTES);
-    if (e != hipSuccess) return mmdm_set_error(MMDM_ERR_HIP, "hipFuncSetAttribute(gemm): %s", hipGetErrorString(e));
-    return MMDM_OK;
-}
-
-template <int TM, int TN, int BK, int AVEC, int WVEC, bool FULL>
-int launch(GemmArgs a, hipStream_t st) {
-    using C_ = Cfg<TM, TN, BK>;
-    a.mt = (a.M + C_::BM - 1) / C_::BM;
-    a.nt = (a.N + C_::BN - 1) / C_::BN;
-    mmdm_note_gemm("gemm_f32<%d,%d,%d>", TM, TN, BK);
-    hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, BK, AVEC, WVEC, FULL>), dim3(a.mt * a.nt), dim3(C_::THREADS), C_::SMEM_BYTES, st, a);
-    return mmdm_check_launch("gemm_f32");
-}
-
-// tile variants (selected per call; MMDM_GEMM_CFG overrides for benchmarking)
-template <int TM, int TN, int BK>
-int launch_cfg(const GemmArgs& a, bool av, bool wv, hipStream_t st) {
-    using C_ = Cfg<TM, TN, BK>;
-    const bool full = av && wv && (a.M % C_::BM == 0) && (a.N % C_::BN == 0) && (a.K % C_::BK == 0) && a.Kw == a.K;
-    if (full) return launch<TM, TN, BK, 4, 4, true>(a, st);
-    if (av && wv) return launch<TM, TN, BK, 4, 4, false>(a, st);
-    if (!av && wv) return launch<TM, TN, BK, 1, 4, false>(a, st);
-    if (av && !wv) return launch<TM, TN, BK, 4, 1, false>(a, st);
-    return launch<TM, TN, BK, 1, 1, false>(a, st);
-}
-
-template <int TM, int TN, int BK>
-int set_attr_cfg() {
-    int rc;
-    if ((rc = set_attr<TM, TN, BK, 4, 4, true>())) return rc;
-    if ((rc = set_attr<TM, TN, BK, 4, 4, false>())) return rc;
-    if ((rc = set_attr<TM, TN, BK, 1, 4, false>())) return rc;
-    if ((rc = set_attr<TM, TN, BK, 4, 1, false>())) return rc;
-    return set_attr<TM, TN, BK, 1, 1, false>();
-}
-
-inline bool vec_ok(const float* p, int ld, int K) {
-    return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0 && (K & 3) == 0;
-}
+inline bool aligned16(const void* p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
 
 }  // namespace
 
-int g_gemm_cfg = -1;
+// mmdm_diag_set switches of this translation unit (include/mmdm.h section 4); process-global, for tests and tools/ only
+int g_gemm_cfg = -1;        // forced kernel (gemm_f32_plan.h: plan()); -1 automatic
 int g_gemm_tail = -1;       // row split of the fractional last round: t > 0: split when the fractional round holds <= t/10 of the resident slots; 0 off;
                             // -1 (default): what the caller's handle asked for through mmdm_gemm_set_tail (one-stream samplers: 10, two-stream: 0)
 static thread_local int t_gemm_tail = 0;
 void mmdm_gemm_set_tail(int t) { t_gemm_tail = t; }
 int mmdm_gemm_get_tail(void) { return t_gemm_tail; }
-int g_gemm_ablate = 0;
 #ifndef MMDM_S16_DEFAULT
 #define MMDM_S16_DEFAULT -1
 #endif
-int g_gemm_s16 = MMDM_S16_DEFAULT;       // mmdm_diag_set "gemm_s16": -1 automatic, 0 off, 13 / 23 / 14 / 24: force <TN16, stages> wherever the kernel covers the call
+int g_gemm_s16 = MMDM_S16_DEFAULT;       // -1 automatic, 0 off, 13 / 23 / 14 / 24: force <TN16, stages> wherever the kernel covers the call
 unsigned long long* g_gemm_stamps = nullptr;
 
 int mmdm_gemm_init(void) {
-    int rc;
-    if ((rc = set_attr_cfg<22, 22, 32>())) return rc;
-    if ((rc = set_attr_cfg<22, 22, 16>())) return rc;
-    if ((rc = set_attr_cfg<22, 12, 16>())) return rc;
-    if ((rc = set_attr_cfg<22, 22, 8>())) return rc;
-    if ((rc = set_attr_cfg<42, 22, 16>())) return rc;
-    if ((rc = set_attr_cfg<22, 42, 16>())) return rc;
-    if ((rc = set_attr_glds<42, 22>())) return rc;
-    if ((rc = set_attr_glds<22, 22>())) return rc;
-    if ((rc = set_attr_glds<22, 21>())) return rc;
-    if ((rc = set_attr_glds<22, 22, 16, 4, 1, 1>())) return rc;
-    if ((rc = set_attr_glds<42, 22, 16, 3, 1, 1>())) return rc;
-    if ((rc = set_attr_glds<22, 21, 16, 3, 1, 1>())) return rc;
-    if ((rc = set_attr_glds<22, 22, 16, 5, 1, 1>())) return rc;
-    if ((rc = set_attr_glds<22, 21, 16, 4, 1, 1>())) return rc;
-    if ((rc = set_attr_glds<22, 21, 16, 5, 1, 1>())) return rc;
-    if ((rc = set_attr_glds<21, 21, 16, 4, 1, 1>())) return rc;
-    if ((rc = set_attr_glds<22, 22, 16, 5, 1, 2>())) return rc;
-    if ((rc = set_attr_glds<22, 22, 16, 5, 1, 3>())) return rc;
-    if ((rc = set_attr_s16<1, 3>())) return rc;
-    if ((rc = set_attr_s16<2, 3>())) return rc;
-    if ((rc = set_attr_s16<1, 4>())) return rc;
-    if ((rc = set_attr_s16<2, 4>())) return rc;
-    if ((rc = set_attr_mix())) return rc;
+    for (const Form& f : FORMS)
+        if (int rc = f.attr()) return rc;
     return MMDM_OK;
 }
 
-// diagnostics of this translation unit (mmdm_diag_set, include/mmdm.h section 4): tile configuration override (-1 = automatic), timing
-// ablation bits, row-split rule override, in-kernel stamp buffer.  Process-global, for tools/ only.
 bool mmdm_diag_gemm_f32(const char* key, long long v) {
     if (!strcmp(key, "gemm_cfg")) g_gemm_cfg = (int)v;
-    else if (!strcmp(key, "gemm_ablate")) g_gemm_ablate = (int)v;
     else if (!strcmp(key, "gemm_tail")) g_gemm_tail = (int)v;
     else if (!strcmp(key, "gemm_s16")) g_gemm_s16 = (int)v;
     else if (!strcmp(key, "gemm_stamps")) g_gemm_stamps = reinterpret_cast<unsigned long long*>((uintptr_t)v);
@@ -1086,110 +1011,23 @@ int mmdm_linear_f32_ex(const float* A, int lda, const float* W, int ldw, int Kw,
     a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ld_extra = ld_extra;
     a.M = M; a.N = N; a.K = K; a.Kw = Kw; a.epilogue = epilogue; a.period = period > 0 ? period : 1;
     a.mt = a.nt = 0;
-    a.ablate = g_gemm_ablate;
     a.stamps = g_gemm_stamps;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool av = vec_ok(A, lda, K), wv = vec_ok(W, ldw, Kw);
-    const bool glds_ok = av && wv && (K % 16 == 0) && Kw == K;
-    // production choice: LDS-DMA kernel, 128x128 tile / 4 waves (5 workgroups per CU) whenever the operands allow it
-    const int tail = g_gemm_tail >= 0 ? g_gemm_tail : t_gemm_tail;
-    switch (g_gemm_cfg) {
-        case 10: if (glds_ok) return launch_glds<42, 22>(a, st); break;
-        case -1:
-            if (glds_ok && K >= 96 && tail && epilogue != MMDM_EPI_BIAS_PE) {
-                // Row split ("tile list" of two entries) for callers that run ONE stream of kernels: M = 12 544 (configs[1]) gives 2352 / 3136 /
-                // 784 tiles for 512 (128x128, two per CU) or 768 (128x64, three per CU) resident slots = 4.6 / 4.1 / 1.5 rounds, and the
-                // fractional round costs a whole tile lifetime on a partly empty chip.  Rows [0, M1) -- as many whole row tiles as fit into
-                // complete rounds -- go to the large tile; the remaining rows to a tile of half / a quarter of the area, whose single
-                // partial round is as short.  Measured: configs[1] 15.35 -> 14.45 ms/step; QKV at M = 19 200 stand-alone 894 -> 857 us.
-                // The two-stream MixerMDM step does NOT use it (59.2 vs 59.5 ms/step: the other stream's kernels already fill a tail).
-                // Every pipelined instantiation accumulates an output element in the same order, so the split does not change a bit
-                // (tests: bitwise batch independence, production tiles vs float64).
-                const bool narrow = N <= 512 || K <= 512 || N == 2048;
-                const long slots = narrow ? 768 : 512, nt = (N + (narrow ? 63 : 127)) / (narrow ? 64 : 128), mt = (M + 127) / 128;
-                const long tiles = mt * nt, full = tiles / slots, rem = tiles - full * slots;
-                const long mt1 = full * slots / nt;
-                if ((long)((M + 127) / 128) * ((N + 63) / 64) >= 512 && full >= 1 && mt1 >= 1 && mt1 < mt && rem * 10 <= slots * tail) {
-                    const int M1 = (int)mt1 * 128;
-                    GemmArgs b = a;
-                    a.M = M1;
-                    b.M = M - M1;
-                    b.A = A + (size_t)M1 * lda;
-                    b.C = C + (size_t)M1 * ldc;
-                    if (extra) b.extra = extra + (size_t)M1 * ld_extra;
-                    int rc = narrow ? launch_glds<22, 21, 16, 4, 1, 1>(a, st) : launch_glds<22, 22, 16, 5, 1, 1>(a, st);
-                    if (rc) return rc;
-                    // remainder: the largest tile that still gives every CU a workgroup
-                    const long r128 = (long)((b.M + 127) / 128) * ((N + 63) / 64);
-                    if (!narrow && r128 >= 256) return launch_glds<22, 21, 16, 4, 1, 1>(b, st);
-                    return launch_glds<21, 21, 16, 4, 1, 1>(b, st);
-                }
-            }
-            if (glds_ok && K >= 96) {
-                // Production: the software-pipelined loop (gemm_pipe).  Tile / stage choice per shape, measured at M = 19 200 with
-                // tools/gemm_bench.py (TFLOP/s; the 2-stage kernels of round 1 reached 100-121 on the same shapes):
-                //   N = 3072, K = 1024 (QKV):        128x128, 5 stages 128      N = 2048, K = 1024 (FFN up, K|V): 128x64, 4 stages 119-122
-                //   N = 1024, K = 1024 / 2048:       128x128, 5 stages 124 / 128   mixer (N or K <= 512):          128x64, 4 stages 107-121
-                // Few tiles (small batches): 64x64 tiles so that every CU has work.  All instantiations accumulate each output element in
-                // the same order (bias + residual first, then k ascending), so a row's result does not depend on the tile that produced it.
-                const long t64 = (long)((M + 127) / 128) * ((N + 63) / 64);
-                if (g_gemm_s16 > 0 && s16_ok(a)) {
-                    switch (g_gemm_s16) {
-                        case 13: return launch_s16<1, 3>(a, st);
-                        case 14: return launch_s16<1, 4>(a, st);
-                        case 24: return launch_s16<2, 4>(a, st);
-                        default: return launch_s16<2, 3>(a, st);
-                    }
-                }
-                // Launches whose 64 x 64 grid leaves half of the CUs idle (configs[0]'s M = 240 against N <= 2048, conditioning / time-embedding rows):
-                // quarter-length chains on 16 x 16 blocks, four times the workgroups, bit-identical (gemm_s16_kernel).  Not the weight-streaming
-                // projections (M <= 64 against N >= 4096: below).
-                if (g_gemm_s16 < 0 && (long)((M + 63) / 64) * ((N + 63) / 64) <= 128 && !(M <= 64 && N >= 4096) && s16_ok(a)) return launch_s16<1, 4>(a, st);
-                // 64 x 64 tiles with a fractional last round (the reference's B = 1 call: 19 row tiles x N / 64 = 1.2 / 2.4 / 3.6 rounds of 256): the rows of
-                // the whole rounds on those tiles, the rest as quarter-length chains beside them, in one launch (gemm_mix_kernel)
-                if (t64 < 512 && g_gemm_s16 < 0 && epilogue != MMDM_EPI_BIAS_PE && s16_ok(a) && vepi_ok(a)) {
-                    // measured (tools/gemm_s16_bench.py, M = 1196; us, 64 x 64 launch -> mixed): N = 1024: 37.6 -> 30.1 (K = 2048: 63.5 -> 50.1), N = 2048: 51.2 -> 47.9,
-                    // N = 3072 (three whole rounds): 79.8 -> 82.7, N = 1536 at K = 512 (more remainder than main tiles): 19.5 -> 23.7 -- the remainder tiles
-                    // cost about twice their matrix-pipe time, so the launch is mixed for one or two whole rounds and a remainder no larger than the main part
-                    const long nt64 = (N + 63) / 64, tiles = (long)((M + 63) / 64) * nt64, rounds = tiles / 256, mt1 = rounds * 256 / nt64;
-                    const long rem_wgs = mt1 * 64 < M ? (long)((M - mt1 * 64 + 31) / 32) * ((N + 31) / 32) : 0;
-                    if (rounds >= 1 && rounds <= 2 && mt1 >= 1 && rem_wgs > 0 && rem_wgs <= mt1 * nt64 && tiles % 256 != 0) return launch_mix(a, (int)mt1 * 64, st);
-                }
-                if (t64 < 512) return launch_glds<21, 21, 16, 4, 1, 1>(a, st);
-                // Skinny M against a wide weight matrix -- the packed AdaLN projections of a step: M = 2B .. 4B conditioning rows, N = L x n_ada x 2D =
-                // 32 768 / 49 152 columns, 134 / 201 MB of fp32 weights read ONCE per step: a weight-streaming launch, not a matrix-pipe one.  The 128 x 128
-                // tile gives it 384 workgroups of 80 KB (two per CU) and multiplies padding rows: 158 us for M = 64, N = 49 152 with W cold (1.3 TB/s);
-                // 64 x 64 tiles (768 workgroups, 32 KB: five per CU, more bytes in flight) 79 us; 128 x 64 for 64 < M <= 256: 134 -> 110 us (M = 128),
-                // 258 -> 207 (M = 256).  Bit-identical like every tile choice (round 6; tools: a probe with W evicted between calls).
-                if (M <= 64 && N >= 4096) return launch_glds<21, 21, 16, 4, 1, 1>(a, st);
-                if (M <= 256 && N >= 4096) return launch_glds<22, 21, 16, 4, 1, 1>(a, st);
-                if (N <= 512 || K <= 512 || N == 2048) return launch_glds<22, 21, 16, 4, 1, 1>(a, st);
-                return launch_glds<22, 22, 16, 5, 1, 1>(a, st);
-            }
-            if (glds_ok) {
-                const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
-                return tiles < 1000 ? launch_glds<22, 21>(a, st) : launch_glds<22, 22>(a, st);
-            }
-            break;
-        case 11: if (glds_ok) return launch_glds<22, 22>(a, st); break;
-        case 17: if (glds_ok) return launch_glds<22, 21>(a, st); break;     // 128 x 64 tile, 4 waves (64 x 32 per wave)
-        case 31: if (glds_ok && K >= 64) return launch_glds<22, 22, 16, 4, 1, 1>(a, st); break;   // ... 4 stages (64 KB: 2 per CU)
-        case 32: if (glds_ok && K >= 64) return launch_glds<42, 22, 16, 3, 1, 1>(a, st); break;   // ... 256 x 128 / 8 waves, 3 stages (72 KB: 2 per CU)
-        case 33: if (glds_ok && K >= 64) return launch_glds<22, 21, 16, 3, 1, 1>(a, st); break;   // ... 128 x 64 / 4 waves
-        case 34: if (glds_ok && K >= 80) return launch_glds<22, 22, 16, 5, 1, 1>(a, st); break;   // ... 128 x 128, 5 stages (80 KB: 2 per CU)
-        case 36: if (glds_ok && K >= 64) return launch_glds<22, 21, 16, 4, 1, 1>(a, st); break;   // ... 128 x 64, 4 stages (48 KB: 3 per CU)
-        case 38: if (glds_ok && K >= 80) return launch_glds<22, 21, 16, 5, 1, 1>(a, st); break;   // ... 128 x 64, 5 stages (60 KB: 2 per CU)
-        case 41: if (glds_ok && K >= 64) return launch_glds<21, 21, 16, 4, 1, 1>(a, st); break;   // ... 64 x 64 / 4 waves of 32 x 32
-        case 60: if (glds_ok && K >= 96) return launch_glds<22, 22, 16, 5, 1, 2>(a, st); break;   // ablation: no LDS-DMA in the main loop
-        case 61: if (glds_ok && K >= 96) return launch_glds<22, 22, 16, 5, 1, 3>(a, st); break;   // ablation: no barrier
-        default: break;
+    const P::Call c = {M, N, K, Kw, epilogue,
+                       aligned16(A, lda), aligned16(W, ldw), aligned16(C, ldc), !bias || aligned16(bias, 0), aligned16(extra, ld_extra),
+                       g_gemm_cfg, g_gemm_tail >= 0 ? g_gemm_tail : t_gemm_tail, g_gemm_s16};
+    const P::Plan plan = P::plan(c);
+    for (int i = 0; i < plan.n; ++i) {
+        const P::Launch& l = plan.l[i];
+        GemmArgs b = a;                                  // this launch's rows: A, C and `extra` start at row0
+        b.M = l.rows;
+        b.A = A + (size_t)l.row0 * lda;
+        b.C = C + (size_t)l.row0 * ldc;
+        if (extra) b.extra = extra + (size_t)l.row0 * ld_extra;
+        char name[64];
+        P::kernel_name(l, N, name, sizeof(name));
+        mmdm_note_gemm("%s", name);
+        if (int rc = FORMS[l.kernel].launch(b, c, l, static_cast<hipStream_t>(stream))) return rc;
     }
-    switch (g_gemm_cfg) {
-        case 0: return launch_cfg<22, 22, 32>(a, av, wv, st);
-        case 2: return launch_cfg<22, 12, 16>(a, av, wv, st);
-        case 3: return launch_cfg<22, 22, 8>(a, av, wv, st);
-        case 5: return launch_cfg<22, 42, 16>(a, av, wv, st);
-        case 4: return launch_cfg<42, 22, 16>(a, av, wv, st);
-        default: return launch_cfg<22, 22, 16>(a, av, wv, st);
-    }
+    return MMDM_OK;
 }
+

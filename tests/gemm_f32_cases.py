@@ -2,7 +2,8 @@
 
 mmdm_linear_f32 (csrc/gemm_f32.hip) picks a kernel from the call's shape, alignment and epilogue alone.  expected_kernel_f32 is this suite's
 statement of that rule (the automatic dispatch, gemm_cfg = -1, without the row split: tail = 0): the exact mmdm_last_gemm_kernel() string of a
-call.  A change of the dispatcher has to edit it knowingly.  The tables below hold, per kernel, the smallest shapes that reach it -- tile
+call; expected_plan_f32 adds the row split (tail > 0).  tests/test_gemm_f32_plan_cpu.py holds csrc/gemm_f32_plan.h to both on the CPU.  A change
+of the dispatcher has to edit them knowingly.  The tables below hold, per kernel, the smallest shapes that reach it -- tile
 edges in M, N and K, and both sides of every threshold -- each with the kernel its comment names (`Entry.kernel`, written out by hand: the CPU
 test holds the mirror to it, the GPU test holds the library to the mirror).
 
@@ -82,6 +83,38 @@ def expected_kernel_f32(M, N, K, epi, *, a_vec=True, w_vec=True, c_al=True, bias
 def mix_split(M, N):
     """M1 of a mixed launch: the rows of the whole rounds of 256 64 x 64 tiles."""
     return 256 * (_cdiv(M, 64) * _cdiv(N, 64) // 256) // _cdiv(N, 64) * 64
+
+
+def narrow_tile(N, K):
+    """Shapes whose pipelined tile is 128 x 64 with 4 stages (768 resident slots: three workgroups per CU), not 128 x 128 with 5 (512)."""
+    return N <= 512 or K <= 512 or N == 2048
+
+
+def expected_plan_f32(M, N, K, epi, *, tail, a_vec=True, w_vec=True, c_al=True, bias_al=True, extra_al=True):
+    """(mmdm_last_gemm_kernel(), M1) of mmdm_linear_f32(M, N, K, epi) under gemm_cfg = -1, gemm_s16 = -1 and the row-split rule `tail` (mmdm_diag_set
+    "gemm_tail", or what the caller's handle set): a call whose 128-row tiles fill at least one whole round of the resident slots and leave a
+    fractional round of at most tail / 10 of them runs rows [0, M1) -- the row tiles of the whole rounds -- on the large tile and the other rows
+    on a smaller one, two launches whose names the note joins with "+".  Never the PE epilogue, only the pipelined kernels (K of 96 and more).  Every
+    other call is the single launch of expected_kernel_f32; M1 is then the cut of a mixed launch (mix_split), else 0."""
+    one = expected_kernel_f32(M, N, K, epi, a_vec=a_vec, w_vec=w_vec, c_al=c_al, bias_al=bias_al, extra_al=extra_al)
+    epi = "resid" if epi == "resid_inplace" else epi
+    glds_ok = a_vec and w_vec and K % 16 == 0
+    if glds_ok and K >= 96 and tail and epi != "pe":
+        narrow = narrow_tile(N, K)
+        slots = 768 if narrow else 512
+        mt, nt = _cdiv(M, 128), _cdiv(N, 64 if narrow else 128)
+        tiles = mt * nt
+        full = tiles // slots
+        rem = tiles - full * slots
+        mt1 = full * slots // nt
+        if mt * _cdiv(N, 64) >= 512 and full >= 1 and 1 <= mt1 < mt and rem * 10 <= slots * tail:
+            M1 = mt1 * 128
+            e = "vepi" if epi == "resid" and N % 4 == 0 and c_al and bias_al and extra_al else "scalar"
+            main = "22,21,16,4" if narrow else "22,22,16,5"
+            # remainder: the largest tile that still gives each of the 256 CUs a workgroup
+            rest = "22,21,16,4" if not narrow and _cdiv(M - M1, 128) * _cdiv(N, 64) >= 256 else "21,21,16,4"
+            return f"gemm_pipe<{main},{e}>+gemm_pipe<{rest},{e}>", M1
+    return one, (mix_split(M, N) if one.startswith("gemm_mix<") else 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

@@ -7,7 +7,8 @@ Kernels (csrc/gemm_f32.hip; the automatic dispatch picks one from the call's sha
   gemm_s16<1,4,late|plain>               16 x 16 chains for launches of few tiles
   gemm_mix<vepi|scalar,a+b>              whole rounds on 64 x 64 tiles + the remaining rows on 16 x 16 chains, one launch
 Every run asserts the instantiation through mmdm_last_gemm_kernel() against tests/gemm_f32_cases.py::expected_kernel_f32, the suite's
-statement of the dispatch rule (held to the tables' hand-written names on the CPU by tests/test_gemm_f32_cases_cpu.py).
+statement of the dispatch rule (held to the tables' hand-written names on the CPU by tests/test_gemm_f32_cases_cpu.py, and csrc/gemm_f32_plan.h
+to it by tests/test_gemm_f32_plan_cpu.py).  The forced kernels (gemm_cfg) run once each on one shape.
 
 The library is called through ctypes, so strides and pointers are the test's own (gemm_f32_cases.layout_f32): A, W and `extra` are windows of
 wider buffers of finite garbage, C is a window [M, N] of a NaN-filled [M + 8, ldc] buffer, and the alignment kinds move one pointer or
@@ -272,6 +273,29 @@ def test_pipe_s16_and_mix_give_the_same_bits(shape):
         assert torch.isfinite(mix).all()
         for what, t in (("gemm_s16", s16), ("gemm_pipe 64 x 64", p64), ("gemm_pipe 64 x 64 under a misaligned bias", off)):
             _assert_bits(t, mix, f"{what} against {k0}, {epi}, {M}x{N}x{K}")
+
+
+FORCED = {1: "gemm_f32<22,22,16>", 11: "gemm_glds<22,22,16,2,{e}>", 17: "gemm_glds<22,21,16,2,{e}>", 34: "gemm_pipe<22,22,16,5,{e}>",
+          36: "gemm_pipe<22,21,16,4,{e}>", 41: "gemm_pipe<21,21,16,4,{e}>"}
+
+
+@pytest.mark.parametrize("cfg", tuple(FORCED))
+def test_forced_kernels_are_bit_exact(cfg):
+    """mmdm_diag_set("gemm_cfg", v) for every value that names a kernel (csrc/gemm_f32_plan.h), on the smallest aligned shape that passes each
+    kernel's K floor and crosses a tile edge in M and N: the named kernel ran, the window equals float64 bit for bit, nothing beside it
+    changed (Placed.run).  A forced pipelined kernel whose A is misaligned is the fallback."""
+    M, N, K = 129, 132, 96
+    for epi, e in (("bias", "scalar"), ("resid", "vepi")):
+        c = F.lattice_case_f32(M, N, K, epi)
+        with diags(gemm_cfg=cfg):
+            got, name = Placed(c).run()
+        assert name == FORCED[cfg].format(e=e), (cfg, epi, name)
+        _assert_bits(got, c.ref().float(), f"gemm_cfg {cfg}: {name} {epi}")
+    if cfg == 34:
+        with diags(gemm_cfg=cfg):
+            got, name = Placed(c, "a_off1").run()
+        assert name == "gemm_f32<22,22,16>", name
+        _assert_bits(got, c.ref().float(), f"gemm_cfg {cfg} under a misaligned A: {name}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

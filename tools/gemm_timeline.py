@@ -9,7 +9,6 @@ d = torch.device("cuda:0")
 shapes = {"out": (19200, 1024, 1024, "resid"), "ffn2": (19200, 1024, 2048, "resid"), "qkv": (19200, 3072, 1024, "bias"), "ffn1": (19200, 2048, 1024, "gelu")}
 ops.linear(torch.zeros(8, 64, device=d), torch.zeros(8, 64, device=d))     # lazy init first (it resets the forced configuration)
 lib.mmdm_diag_set(b"gemm_cfg", int(os.environ.get("CFG", "-1")))
-lib.mmdm_diag_set(b"gemm_ablate", int(os.environ.get("ABL", "0")))
 for name in (sys.argv[1:] or ["out", "qkv"]):
     M, N, K, epi = shapes[name]
     x = torch.randn(M, K, device=d); w = torch.randn(N, K, device=d) / math.sqrt(K); b = torch.randn(N, device=d)
